@@ -1,12 +1,18 @@
 """bench.py — Neural Body hot-path throughput on MI355X.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
+A plain run sets up, warms up, times the K steps and prints the result line (throughput, ms_per_step, the roofline of the
+timed march launches).  `--full` adds everything else the benchmark measures behind the timed region: the parity check against
+the CPU oracle, the CPU baseline, the informational `extras` (turntable, training step, exact-fp32 view, mask-culled renderers,
+encoder, 8-way split proxy), the strictly serial `serial_ms_per_step` and, under a launcher, the `strong_leg`.
+`--dump-outputs DIR` writes what the last timed step returned to its caller as DIR/<name>.npy (dump_outputs).
+
 Run it from the repository checkout: the synthetic scenes are test infrastructure (tests/synthetic.py, imported as
 `tests.synthetic`), as is the CPU oracle the parity and cpu_baseline legs call (oracle/).  `python bench.py --gpus N` with N > 1 and
-no launcher around it re-executes itself under torch.distributed.run (self_launch); an N > 1 weak run also carries a strong leg
+no launcher around it re-executes itself under torch.distributed.run (self_launch); an N > 1 weak --full run also carries a strong leg
 (`strong_leg`: one view per step, its rays split over the ranks) behind the timed region.
 
 Workload (BASELINE.json `metric`): synthetic 6890-vertex SMPL scene, 512x512 image whose every pixel
@@ -25,7 +31,7 @@ cannot sign, |sigma_last| < FP32_SIGMA, bounded by its T_last); `parity_linf` is
 density is within ILL_SIGMA of zero, which `parity` lists one by one together with what the march's last-sample fix-up did.
 `--scaling strong` shards ONE view's rays over the ranks (parallel.render_sharded) instead of one view per rank.
 
-The JSON line also carries
+The JSON line also carries (cpu_baseline with --full only)
   roofline     — the dominant kernel (nb_march_fold_kernel by default; --precision f32 picks the exact one): algorithmic MLP
                  flops (859 904 per ray-sample) / its average launch duration measured with HIP
                  events inside the timed region, against the dense MFMA peak of the arithmetic its main product runs on
@@ -717,11 +723,41 @@ def encoder_bench(args, dev):
                             "is ahead (profiles/r05_step_timeline.md: the same from a rocprofv3 trace); launches = those events"}
 
 
+DUMP_MAX_BYTES = 64 << 20
+DUMP_SAMPLE_BYTES = 16 << 20  # an output larger than this is written as a fixed, seeded sample of its rays
+DUMP_SAMPLE_SEED = 0
+
+
+def dump_outputs(out_dir, outputs):
+    """--dump-outputs DIR: every array of `outputs` (what the last timed step returned to its caller, tensors of [1, rays, ...])
+    as DIR/<name>.npy, float32 (float64 stays float64).  An array larger than DUMP_SAMPLE_BYTES — the per-sample `weights`,
+    [1, 262 144, 64] on the bench view — is written as DIR/<name>_sample.npy: the rays picked by a generator seeded with
+    DUMP_SAMPLE_SEED, in ascending order, the same rays in every run of the same arguments."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {}
+    for name, t in outputs.items():
+        a = t.detach().cpu()
+        a = (a if a.dtype == torch.float64 else a.float()).numpy()
+        if a.nbytes > DUMP_SAMPLE_BYTES:
+            n = a.shape[1]
+            keep = max(1, int(n * DUMP_SAMPLE_BYTES // a.nbytes))
+            rows = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, size=keep, replace=False))
+            name, a = name + "_sample", a[:, rows]
+        arrays[name] = np.ascontiguousarray(a)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit("--dump-outputs: %d bytes exceed the %d-byte budget" % (total, DUMP_MAX_BYTES))
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def self_launch(n, argv, dry_run=False):
-    """`python bench.py --gpus N` started on its own (no RANK / WORLD_SIZE in the environment): replace this process by
-    `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port <free> bench.py <argv>` —
-    one rank per GPU, the launch the driver's own N > 1 command uses.  Refuses when the box has fewer than N devices."""
+    """`python bench.py --gpus N` started on its own (no RANK / WORLD_SIZE in the environment): run
+    `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port <free> bench.py <argv>` as
+    a child process and exit with its status — one rank per GPU, the launch the driver's own N > 1 command uses.  Refuses when the
+    box has fewer than N devices."""
     import socket
+    import subprocess
 
     if not dry_run:
         have = torch.cuda.device_count() if torch.cuda.is_available() else 0
@@ -738,7 +774,8 @@ def self_launch(n, argv, dry_run=False):
     sys.stdout.flush()
     sys.stderr.write("[bench] --gpus %d without a launcher: re-executing under torch.distributed.run (port %d)\n" % (n, port))
     sys.stderr.flush()
-    os.execve(sys.executable, cmd, env)
+    rc = subprocess.run(cmd, env=env).returncode
+    raise SystemExit(rc if rc >= 0 else 128 - rc)  # a launcher killed by signal s: the shell's 128 + s
 
 
 def dry_run(args, emit, rank, world):
@@ -801,7 +838,14 @@ def main():
     ap.add_argument("--encoder-graph", action="store_true",
                     help="the prefetched encoder pass as ONE HIP graph launch (Renderer.use_encoder_graph): 1.01 -> 0.67 ms per pass on an idle "
                          "device, 20 us of host time instead of 1 ms; behind a march it changes nothing (profiles/r06_encoder_graph.md)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the parity check, the CPU baseline, the extras, the serial leg and (under a "
+                         "launcher) the strong leg; a plain run only times the steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the arrays the last timed step returned as DIR/<name>.npy (float32, at most 64 MB in all)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.gpus > 1 and "RANK" not in os.environ and "WORLD_SIZE" not in os.environ:
         self_launch(args.gpus, sys.argv[1:], args.dry_run)  # does not return
 
@@ -871,6 +915,8 @@ def main():
     tickets = {}  # view index -> ticket of its encoder pass, args.prefetch_depth views ahead
 
     def step(i):
+        """One step; returns what its caller receives: the render's maps (strong: the all-gathered rgb_map of the view; weak
+        under a launcher: also the all-gathered RGB tiles of all ranks' views)."""
         # weak: rank r renders view i + r (N different views per step); strong: every rank works on the SAME view i
         off = rank if args.scaling == "weak" else 0
         b = poses[(i + off) % len(poses)]
@@ -880,7 +926,7 @@ def main():
         # every step still encodes one frame and marches one view, the encoder's ~60 small launches run in the march's shadow
         fence = rend.fence() if overlap[0] else None
         if args.scaling == "strong":
-            out = render_sharded(rend, b, dist.group.WORLD if dist is not None else None, prefetched=cur)["rgb_map"][0]
+            out = render_sharded(rend, b, dist.group.WORLD if dist is not None else None, prefetched=cur)
             if overlap[0]:
                 tickets[ahead] = rend.prefetch(poses[(ahead + off) % len(poses)], after=fence)
             return out
@@ -893,8 +939,8 @@ def main():
             tiles = all_gather_tiles(out["rgb_map"][0], dist.group.WORLD)
             g1.record()
             gather_events.append((g0, g1))
-            return tiles
-        return out["rgb_map"][0]
+            return dict(out, rgb_tiles_all_ranks=tiles[None])
+        return out
 
     with torch.no_grad():
         for i in range(args.warmup):
@@ -906,25 +952,34 @@ def main():
         ops.MARCH_EVENTS = []
         step_events = []
         del gather_events[:]
+        last = None
         t0 = time.perf_counter()
         for i in range(args.steps):
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
-            step(args.warmup + i)
+            out = step(args.warmup + i)
             e1.record()
             step_events.append((e0, e1))
+            if args.dump_outputs and i == args.steps - 1:
+                last = out
+            del out
         torch.cuda.synchronize()
         if dist is not None:
             dist.barrier()
         torch.cuda.synchronize()
         elapsed = time.perf_counter() - t0
         events, ops.MARCH_EVENTS = ops.MARCH_EVENTS, None
-        # N > 1 (any run under a launcher), weak headline: a STRONG leg behind the timed region — the same poses, one view per
-        # step with its rays split over the ranks (whole 8-row tile bands) and the RGB tiles all-gathered: north_star's "partition
-        # pixel batches across the 8 GPUs".  Its speed-up is quoted against the weak leg's step (one whole view per GPU).
+        if last is not None:
+            if rank == 0:
+                dump_outputs(args.dump_outputs, last)
+            last = None
+        # N > 1 (any run under a launcher), weak headline, --full: a STRONG leg behind the timed region — the same poses, one view
+        # per step with its rays split over the ranks (whole 8-row tile bands) and the RGB tiles all-gathered: north_star's
+        # "partition pixel batches across the 8 GPUs".  Its speed-up is quoted against the weak leg's step (one whole view per GPU).
+        want_strong_leg = dist is not None and args.scaling == "weak" and args.full and not args.no_strong_leg
         strong_leg = None
         strong_error = None
-        if dist is not None and args.scaling == "weak" and not args.no_strong_leg:
+        if want_strong_leg:
             try:  # the headline above must survive whatever this informational leg does
                 stickets = {}
 
@@ -968,9 +1023,9 @@ def main():
             except Exception as e:  # noqa: BLE001
                 strong_leg, strong_error = None, repr(e)
                 ops.MARCH_EVENTS = None
-        # the same steps strictly serial on one stream (informational: what a single render() call costs)
+        # --full: the same steps strictly serial on one stream (informational: what a single render() call costs)
         serial_ms = None
-        if overlap[0] and dist is None:
+        if args.full and overlap[0] and dist is None:
             overlap[0] = False
             base = args.warmup + args.steps
             for i in range(args.prefetch_depth + 1):
@@ -999,7 +1054,7 @@ def main():
                                        dist.group.WORLD, dev)
         per_rank = [{"rank": r, "march_ms": row[0], "allgather_ms": row[1], "median_step_ms": row[2]} for r, row in enumerate(rows)]
         # every rank must agree that the leg ran before they meet in its reduction (a rank that raised would leave the others waiting)
-        if not args.no_strong_leg and args.scaling == "weak":
+        if want_strong_leg:
             okf = torch.tensor([1.0 if strong_leg is not None else 0.0], dtype=torch.float64, device=dev)
             dist.all_reduce(okf, op=dist.ReduceOp.MIN, group=dist.group.WORLD)
             if float(okf.item()) < 1.0:
@@ -1041,7 +1096,7 @@ def main():
                                "Renderer.render = encoder + fused march, %s; the timed region cycles through %d camera poses; %s" % (
                                    H, W, S, "one view per GPU per step" if args.scaling == "weak" else "one view per step, rays split over the GPUs", len(poses),
                                    "every step encodes one frame and marches one view, the encoder of step i + 1 enqueued on a second HIP stream "
-                                   "before the march of step i (Renderer.prefetch; serial_ms_per_step: the same steps on one stream)"
+                                   "before the march of step i (Renderer.prefetch; serial_ms_per_step, with --full: the same steps on one stream)"
                                    if overlap[0] else "encoder and march one after the other on one stream"),
                    "encoder_overlap": bool(overlap[0]), "encoder_graph": bool(getattr(rend, "use_encoder_graph", False)),
                    "rays_per_view": n_rays, "out_sh": [int(s) for s in body["out_sh"]],
@@ -1074,9 +1129,9 @@ def main():
         result["strong_leg"] = strong_leg
     if net.precision == "auto":
         result["config"]["auto"] = {"chosen": net.march_precision(), "six_bit_small_fraction_worst_layer": net._auto[2] if net._auto else None}
-    if rank == 0 and world == 1 and not args.no_extras:
+    if args.full and rank == 0 and world == 1 and not args.no_extras:
         result["extras"] = extras(args, dev)  # before the CPU legs: their thread pools compete with the launch thread
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         par = parity_check(sd, net, rend, poses[1], S)
         result["parity_linf"] = par["linf"]
         result["parity_linf_all"] = par["linf_all"]

@@ -93,14 +93,14 @@ def test_bench_under_torch_distributed_run():
     for scaling in ("weak", "strong"):
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
                "--master-port", "29547", os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
-               "--no-cpu-baseline", "--no-extras", "--size", "128", "--scaling", scaling]
+               "--no-cpu-baseline", "--no-extras", "--size", "128", "--scaling", scaling, "--full"]
         env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
         out = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
         assert out.returncode == 0, out.stderr[-2000:]
         line = [l for l in out.stdout.splitlines() if l.startswith("{")][-1]
         j = json.loads(line)
         assert j["n_gpus"] == 1 and j["scaling"] == scaling and j["value"] > 0 and j["roofline"]["avg_launch_ms"] > 0
-        if scaling == "weak":  # a weak run under a launcher carries the strong leg (one view per step, rays split over the ranks)
+        if scaling == "weak":  # a weak --full run under a launcher carries the strong leg (one view per step, rays split over the ranks)
             sl = j["strong_leg"]
             assert sl["ms_per_step"] > 0 and sl["per_rank"][0]["march_ms"] > 0 and sl["per_rank"][0]["allgather_ms"] > 0
             assert 0.2 < sl["measured_speedup_vs_one_gpu_view"] < 5.0  # one rank, a 128 x 128 view, 2 steps: the same work, give or take the launch thread
@@ -108,17 +108,30 @@ def test_bench_under_torch_distributed_run():
             assert "strong_leg" not in j
 
 
-def test_bare_bench_command():
+def test_bare_bench_command(tmp_path):
     """`python bench.py --gpus 1 ...` exactly as the driver types it (no launcher, no RANK in the environment): one process, no
-    process group, the JSON line with roofline and parity objects."""
+    process group, the JSON line with the roofline object and nothing of what --full adds; --dump-outputs writes the maps of the
+    last timed step."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--no-extras",
-                          "--no-cpu-baseline", "--size", "128"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
+    dump = tmp_path / "outputs"
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--no-extras",
+                          "--no-cpu-baseline", "--size", "128", "--dump-outputs", str(dump)], cwd=ROOT, env=env, capture_output=True,
+                         text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
     j = json.loads(lines[0])
     assert j["n_gpus"] == 1 and j["value"] > 0 and "per_rank" not in j and "strong_leg" not in j
+    assert j["steps"] == 3 and len(j["step_ms"]) == 3 and j["ms_per_step"] > 0 and j["roofline"]["avg_launch_ms"] > 0
+    assert not {"extras", "cpu_baseline", "parity", "serial_ms_per_step"} & set(j)
+    n = 128 * 128
+    shapes = {"rgb_map": (1, n, 3), "disp_map": (1, n), "acc_map": (1, n), "depth_map": (1, n), "weights": (1, n, 64)}
+    assert sorted(p.name for p in dump.iterdir()) == sorted(k + ".npy" for k in shapes)
+    for k, shape in shapes.items():
+        a = np.load(str(dump / (k + ".npy")))
+        assert a.dtype == np.float32 and a.shape == shape and np.isfinite(a).all(), k
+    rgb = np.load(str(dump / "rgb_map.npy"))
+    assert rgb.min() >= 0.0 and rgb.max() <= 1.0 + 1e-5 and rgb.max() > 0.0
     # --gpus 2 on this one-GPU box: refused with a message, not a traceback (the launcher checks the device count first)
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1"], cwd=ROOT, env=env,
                          capture_output=True, text=True, timeout=600)
