@@ -21,6 +21,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
+from ._memo import Memo, tkey
 
 N_VERTS = 6890
 CODE_DIM = 16
@@ -51,8 +52,8 @@ class FeatureVolumes(Sequence):
     [capacity, C]; `shapes[l]` = (D, H, W)): the default arithmetic 'f16f6' marches the fc_0-folded planes, which nb_fold_build
     forms from the compact rows, and never reads a dense volume — 137 MB per frame at out_sh (96, 352, 192) that nothing would
     look at.  Indexing, iterating or `dense()` materialises them (zero fill + scatter on the device, no synchronisation):
-    `calculate_density(_color)` with precision 'f32', foreign consumers, the tests.  `fold`: (fc_0 weight key, storage,
-    ops.fold_build result), rebuilt when the weight changes; a plain list of volumes from elsewhere gets its active set from
+    `calculate_density(_color)` with precision 'f32', foreign consumers, the tests.  `_memo` keeps the fold planes of the volumes
+    per fc_0 weight version (they live as long as the volumes); a plain list of volumes from elsewhere gets its active set from
     ops.sparsify."""
 
     def __init__(self, volumes=None, sparse=None, rows=None, shapes=None, zeroed_int=None):
@@ -63,7 +64,7 @@ class FeatureVolumes(Sequence):
         if shapes is None and volumes is not None:  # [1,C,D,H,W] views or channels-last [D,H,W,C] storage
             shapes = [tuple(int(x) for x in (v.shape[2:] if v.dim() == 5 else v.shape[:3])) for v in volumes]
         self.shapes = shapes
-        self.fold = None
+        self._memo = Memo()
         if self._dense is None and rows is None:
             raise ValueError("FeatureVolumes needs the dense volumes or the levels' compact rows")
 
@@ -172,47 +173,38 @@ class SparseConvNet(nn.Module):
         super().__init__()
         for name, cin, cout, n, stride in ENCODER_BLOCKS:
             setattr(self, name, _block(cin, cout, n, stride))
-
-    @staticmethod
-    def _wkey(conv):
-        w = conv.weight.detach()
-        return w, (w.untyped_storage(), w.data_ptr(), w._version)
-
-    @staticmethod
-    def _fresh(old, key):
-        return old is not None and old[0][0]._cdata == key[0]._cdata and old[0][1:] == key[1:]
+        self._memo = Memo()  # slot (conv, backward_input): the packed forms of the convolutions' weights
 
     def _packed16(self, conv, backward_input=False):
         """fp16 head / remainder B fragments of one convolution's weight (backward_input: the bf16 pairs of its backward-input
-        convolution), rebuilt when the parameter changes (the entry holds the storage it was packed from, so its address cannot
-        be recycled under the key)."""
-        w, key = self._wkey(conv)
-        attr = "_nb_packed16_bwd" if backward_input else "_nb_packed16"
-        old = getattr(conv, attr, None)
-        if not self._fresh(old, key):
-            old = (key, ops.enc_conv_pack16(w, backward_input=backward_input))
-            setattr(conv, attr, old)
-        return old[1]
+        convolution), rebuilt when the parameter changes."""
+        return self._memo.get((conv, backward_input), tkey(conv.weight),
+                              lambda: ops.enc_conv_pack16(conv.weight.detach(), backward_input=backward_input))
 
     def repack_stale(self, with_backward):
         """Every stale packed form of the >= 32-channel convolutions in ONE launch (after an optimiser step all of them are stale:
-        14 forward forms + 14 backward-input forms = 28 launches otherwise)."""
-        jobs, slots = [], []
+        14 forward forms + 14 backward-input forms = 28 launches otherwise).  Returns {conv: its forward form}."""
+        forms, jobs, slots = {}, [], []
         for name, cin, cout, n, stride in ENCODER_BLOCKS:
             block = getattr(self, name)
             for j in range(n):
                 conv = block[3 * j]
                 if int(conv.weight.shape[3]) < 32:
                     continue
-                w, key = self._wkey(conv)
-                forms = [("_nb_packed16", False)] + ([("_nb_packed16_bwd", True)] if with_backward else [])
-                for attr, bwd in forms:
-                    if not self._fresh(getattr(conv, attr, None), key):
-                        jobs.append((w, bwd))
-                        slots.append((conv, attr, key))
+                key = tkey(conv.weight)
+                for bwd in (False, True) if with_backward else (False,):
+                    packed = self._memo.get((conv, bwd), key)
+                    if packed is None:
+                        jobs.append((conv.weight.detach(), bwd))
+                        slots.append(((conv, bwd), key))
+                    elif not bwd:
+                        forms[conv] = packed
         if jobs:
-            for (conv, attr, key), packed in zip(slots, ops.enc_conv_pack16_batch(jobs)):
-                setattr(conv, attr, (key, packed))
+            for (slot, key), packed in zip(slots, ops.enc_conv_pack16_batch(jobs)):
+                self._memo.get(slot, key, lambda: packed)
+                if not slot[1]:
+                    forms[slot[0]] = packed
+        return forms
 
     def forward(self, codes, coord, out_sh, training, save=None, dense=True):
         """codes [6890,16] fp32, coord [6890,3] int32 (d,h,w) -> 4 channels-last volumes [D,H,W,C].
@@ -272,8 +264,7 @@ class SparseConvNet(nn.Module):
         # next to them — the backward pass differentiates the exact-fp32 formulas on those.  NB_ENC_SPLIT=0 keeps every
         # layer on the exact-fp32 MFMA kernel.
         fast = ENC_SPLIT
-        if fast:
-            self.repack_stale(with_backward=save is not None)
+        packed16 = self.repack_stale(with_backward=save is not None) if fast else None
         rows_are_split = False
         rows_f32 = rows  # the fp32 form of the current layer's input rows (what the backward record keeps)
         for li, (name, cin, cout, n, stride, j) in enumerate(layers):
@@ -288,7 +279,7 @@ class SparseConvNet(nn.Module):
                 out_grid, out_lin, n_out, n_out_max, out_dhw = grid, rows_lin, n_rows, n_max, dhw
             if rows_are_split:
                 new_rows, stats = ops.enc_conv16(rows, grid, dhw, out_lin, n_out, n_out_max, out_dhw, stride,
-                                                 self._packed16(conv), cin, cout, stats=stats_all[li, :2 * cout])
+                                                 packed16[conv], cin, cout, stats=stats_all[li, :2 * cout])
             else:
                 new_rows, stats = ops.enc_conv(rows, grid, dhw, out_lin, n_out, n_out_max, out_dhw, stride,
                                                conv.weight.detach(), stats=stats_all[li, :2 * cout])
@@ -349,14 +340,10 @@ class Network(nn.Module):
         # 'f16f6': the march lists the rays whose LAST density it cannot sign (the reference's 1e10 interval makes that sample's alpha
         # a step function, nerf_net_utils.py:28) and recomputes those at fp32 level (include/nb_hip.h, nb_march `ill_scratch`)
         self.last_sample_fixup = os.environ.get("NB_LAST_SAMPLE_FIXUP", "1") != "0"
-        self._auto = None  # (weight key, chosen arithmetic, statistic) of precision 'auto'
-        self._lb_cache = None  # (latent_index tensor, versions, bias) of latent_bias()
-        self._foreign_fold = None  # (volume tensors + versions, fc_0 key, storage, planes) of volumes that came as a plain list
-        self._sat_checked = None  # fc_0 weight key whose first fold build had its saturation count read (precision 'auto')
-        self._planes_overflow = None  # ... and, if that count was not zero, the key again: 'auto' = 'f32' for these weights
+        # the caches of the parameters and of the last frame (packed weights, 'auto''s choice, latent bias, pose block, planes of
+        # foreign volumes, fc_0's saturation state, t_vals): neither copied nor pickled
+        self._memo = Memo(t_vals=4)
         self.last_ill = None
-        self._pose_cache = None  # (R, Th, bounds tensors, versions, the 15-float pose block) of the last make_scene
-        self._sat_pending = None  # (fc_0 key, counter tensor) of a later frame's planes, read at the next host synchronisation
         if int(xyz_res) != 10 or int(view_res) != 4:
             raise NotImplementedError(
                 "xyz_res=10, view_res=4 only: the reference's own Network hard-codes view_fc = Conv1d(346, 128, 1) "
@@ -375,30 +362,6 @@ class Network(nn.Module):
         self.latent_fc = nn.Conv1d(384, 256, 1)
         self.view_fc = nn.Conv1d(346, 128, 1)
         self.rgb_fc = nn.Conv1d(128, 3, 1)
-        self._packed = None
-        self._packed_key = None
-        self._packed_have = set()
-        self._t_vals = {}
-
-    # the packed blobs and their keys (storages!) are caches of the parameters: they are neither copied nor pickled
-    def __getstate__(self):
-        st = dict(self.__dict__)
-        st.update(_packed=None, _packed_key=None, _packed_have=set(), _auto=None, _t_vals={}, _lb_cache=None, _foreign_fold=None,
-                  _sat_checked=None, _planes_overflow=None, _sat_pending=None, last_ill=None, _pose_cache=None)
-        return st
-
-    def __deepcopy__(self, memo):
-        import copy
-
-        cls = self.__class__
-        new = cls.__new__(cls)
-        memo[id(self)] = new
-        for k, v in self.__getstate__().items():
-            setattr(new, k, copy.deepcopy(v, memo))
-        for m in new.modules():
-            m.__dict__.pop("_nb_packed16", None)
-            m.__dict__.pop("_nb_packed16_bwd", None)
-        return new
 
     # ------------------------------------------------------------------ packed decoder weights
     def _mlp_param_dict(self):
@@ -422,12 +385,11 @@ class Network(nn.Module):
         alone — decided once per weight version (one 3-float read-back after packing), the same on every rank, no timing."""
         if self.precision != "auto":
             return self.precision
-        if self._planes_overflow is not None:
-            w = self.fc_0.weight
-            if self._planes_overflow == (w.data_ptr(), w._version):
-                return "f32"  # fc_0 . V does not fit the fp16 planes (nb_fold_build's count, _auto_checks_planes)
-        packed = self.packed_weights("f16f6")
-        if self._auto is None or self._auto[0] is not self._packed_key:
+        if self._saturation().get("overflow"):
+            return "f32"  # fc_0 . V does not fit the fp16 planes (nb_fold_build's count, _auto_checks_planes)
+        key, packed = self._pack({"f16f6"})
+
+        def choose():
             worst = float(ops.six_bit_small_fraction(packed).max())
             choice = "f16f6" if worst <= SIX_BIT_MAX_SMALL else "f32"
             if choice == "f32":
@@ -435,52 +397,46 @@ class Network(nn.Module):
 
                 warnings.warn("neuralbody_amd: %.0f %% of a decoder layer's weights lie below 1/8 of their 32-wide block maximum; "
                               "precision 'auto' takes the exact fp32 kernel for these weights" % (100 * worst))
-            self._auto = (self._packed_key, choice, worst)
-        return self._auto[1]
+            return key, choice, worst
+
+        return self._memo.get("auto", key, choose)[1]
+
+    @property
+    def _auto(self):
+        """(weight key, chosen arithmetic, statistic) of precision 'auto''s six-bit check, None before the first one."""
+        return self._memo.peek("auto")
 
     def packed_weights(self, precision=None):
         """MFMA-ordered decoder blob, rebuilt (on device) whenever a parameter changed; only the sections of the
         arithmetics asked for since the last change are (re)written — a training step repacks every iteration and only
         ever decodes with 'f32'."""
-        need = {self.march_precision()} if precision is None else {precision}
-        d = self._mlp_param_dict()
-        # keyed on the parameters' storages, which the entry keeps alive (so an address cannot be recycled under the
-        # key), and on their version counters (optimizer steps and load_state_dict write in place)
-        key = tuple((t.untyped_storage(), t.data_ptr(), t._version) for t in d.values())
-        old = self._packed_key
-        same = old is not None and len(old) == len(key) and all(
-            a[0]._cdata == b[0]._cdata and a[1:] == b[1:] for a, b in zip(old, key))
-        if self._packed is None or not same:
-            self._packed = ops.mlp_pack(d, self._packed, precisions=need)
-            self._packed_key = key
-            self._packed_have = set(need) | {"f32"}
-        elif not need <= self._packed_have:
-            ops.mlp_pack(d, self._packed, precisions=need - self._packed_have)
-            self._packed_have |= need
-        return self._packed
+        return self._pack({self.march_precision()} if precision is None else {precision})[1]
 
-    def latent_bias(self, latent_index):
-        """Per-frame bias of the merged feature_fc/latent_fc layer (latent_xyzc.py:108-111)."""
-        w = self.latent.weight.detach()
-        # The bias is a function of the frame's latent row and four layers' parameters: kept per (latent_index tensor, its
-        # version, the parameters' versions) — a view loop re-renders one frame, and the three launches it takes (index_select,
-        # copy, nb_mlp_latent_bias: ~40 us) sit between the encoder and the march.  The entry holds the index tensor itself,
-        # so its address cannot be recycled under the key; a training step bumps the versions and misses.
-        d = None
-        if isinstance(latent_index, torch.Tensor):
-            d = self._mlp_param_dict()
-            vers = (latent_index._version, w._version, w.data_ptr()) + tuple((t.data_ptr(), t._version) for t in d.values())
-            old = self._lb_cache
-            if old is not None and old[0] is latent_index and old[1] == vers:
-                return old[2]
-        else:
-            latent_index = torch.tensor([int(latent_index)])
-        idx = latent_index.reshape(-1)[:1].long().to(w.device)
-        row = w.index_select(0, idx)[0].contiguous()
-        lb = ops.mlp_latent_bias(self._mlp_param_dict(), row)
-        if d is not None:
-            self._lb_cache = (latent_index, vers, lb)
-        return lb
+    def _pack(self, need):
+        """(parameter key, blob with the sections of the arithmetics `need`); new parameters repack into the previous blob."""
+        d = self._mlp_param_dict()
+        key = tkey(*d.values())
+        old = self._memo.peek("packed")
+        blob, have = self._memo.get("packed", key, lambda: (ops.mlp_pack(d, None if old is None else old[0], precisions=need),
+                                                            set(need) | {"f32"}))
+        if not need <= have:
+            ops.mlp_pack(d, blob, precisions=need - have)
+            have |= need
+        return key, blob
+
+    def latent_bias(self, latent_index, frame_token=None):
+        """Per-frame bias of the merged feature_fc/latent_fc layer (latent_xyzc.py:108-111), kept per (latent_index tensor, frame
+        token, parameters): a view loop re-renders one frame, and the three launches it takes (~40 us) sit between encoder and march."""
+        def build():
+            w = self.latent.weight.detach()
+            li = latent_index if isinstance(latent_index, torch.Tensor) else torch.tensor([int(latent_index)])
+            row = w.index_select(0, li.reshape(-1)[:1].long().to(w.device))[0].contiguous()
+            return ops.mlp_latent_bias(self._mlp_param_dict(), row)
+
+        if not isinstance(latent_index, torch.Tensor):
+            return build()
+        key = (tkey(latent_index, self.latent.weight, *self._mlp_param_dict().values()), frame_token)
+        return self._memo.get("latent_bias", key, build)
 
     # ------------------------------------------------------------------ scene description
     def make_scene(self, feature_volume, sp_input, precision=None):
@@ -501,96 +457,107 @@ class Network(nn.Module):
         out_sh = [int(s) for s in sp_input["out_sh"]]
         fold = self._fold_planes(feature_volume, vols) if precision == "f16f6" else None
         dev = feature_volume.rows[0].device if lazy else vols[0].device
-        return ops.make_scene(vols, self._pose_block(R, Th, bounds, dev), self.voxel_size, out_sh, fold=fold)
+        pose = self._pose_block(R, Th, bounds, dev, sp_input.get("_frame_token"))
+        return ops.make_scene(vols, pose, self.voxel_size, out_sh, fold=fold)
 
-    def _pose_block(self, R, Th, bounds, dev):
-        """ops.make_pose, kept per (R, Th, bounds) tensor objects and versions: a loop over the views of one frame (and the two
-        make_scene calls of a prefetched render) builds the 15-float block once instead of one concatenation launch each time.  The
-        entry holds the tensors themselves, so an address cannot be recycled under the key (tests/test_gpu_frames.py)."""
-        c = self._pose_cache
-        if (c is not None and all(isinstance(t, torch.Tensor) for t in (R, Th, bounds)) and c[0] is R and c[1] is Th and c[2] is bounds
-                and c[3] == (R._version, Th._version, bounds._version, str(dev))):
-            return c[4]
-        pose = ops.make_pose(R, Th, bounds, device=dev)
-        if all(isinstance(t, torch.Tensor) for t in (R, Th, bounds)):
-            self._pose_cache = (R, Th, bounds, (R._version, Th._version, bounds._version, str(dev)), pose)
-        return pose
+    def _pose_block(self, R, Th, bounds, dev, frame_token):
+        """ops.make_pose, kept per (R, Th, bounds tensors, frame token): a loop over the views of one frame (and the two make_scene
+        calls of a prefetched render) builds the 15-float block once instead of one concatenation launch each time
+        (tests/test_gpu_frames.py)."""
+        if not all(isinstance(t, torch.Tensor) for t in (R, Th, bounds)):
+            return ops.make_pose(R, Th, bounds, device=dev)
+        return self._memo.get("pose", (tkey(R, Th, bounds), str(dev), frame_token),
+                              lambda: ops.make_pose(R, Th, bounds, device=dev))
 
     def _fold_planes(self, feature_volume, vols):
         """(NbFold, keepalive) of the volumes: from the encoder's compact rows when the FeatureVolumes object carries them (no
         dense volume is touched), from its dense volumes + index structures otherwise; a plain list of dense volumes gets its
-        active set from ops.sparsify, sized by ONE read-back of the four counts and kept per (volume tensors, versions, fc_0)."""
-        w = self.fc_0.weight.detach()
-        key = (w.data_ptr(), w._version)
+        active set from ops.sparsify, sized by ONE read-back of the four counts and kept per (volume tensors, fc_0)."""
+        w = self.fc_0.weight
         fv = feature_volume if isinstance(feature_volume, FeatureVolumes) else None
-        if fv is not None and fv.fold is not None and fv.fold[0] == key and fv.fold[1] is w.untyped_storage():
-            return fv.fold[2]
         if fv is not None and fv.sparse is not None:
-            n_sat, fv.zeroed_int = fv.zeroed_int, None  # (a rebuild for a new fc_0 gets a fresh counter)
-            if fv.rows is not None:
-                fold = ops.fold_build(fv.shapes, fv.sparse, w, rows=fv.rows, n_sat=n_sat)
-            else:
-                fold = ops.fold_build(vols, fv.sparse, w, n_sat=n_sat)
-            fv.fold = (key, w.untyped_storage(), fold)  # holds the storage: its address cannot be recycled under the key
-            self._auto_checks_planes(key, fold)
-            return fold
-        # volumes from elsewhere (cloned, loaded, another encoder's): nothing to hang a cache on but the tensors themselves
-        # (`vols` are fresh channels-last VIEWS of the caller's tensors at every call: the key is their storage, address and version;
-        # the entry keeps the views, hence the storages, alive, so an address cannot be recycled under it)
-        fkey = tuple((v, v.untyped_storage()._cdata, v.data_ptr(), v._version, tuple(v.shape)) for v in vols)
-        old = self._foreign_fold
-        if old is not None and old[1] == key and old[2] is w.untyped_storage() and len(old[0]) == len(fkey) and \
-                all(a[1:] == b[1:] for a, b in zip(old[0], fkey)):
-            return old[3]
-        sparse = [ops.sparsify(v) for v in vols]
-        counts = torch.cat([sp[2] for sp in sparse]).tolist()  # one read-back: a capacity of every voxel would be ~1 GB of planes
-        sparse = [(g, lin, n, max(int(c), 1)) for (g, lin, n, _), c in zip(sparse, counts)]
-        fold = ops.fold_build(vols, sparse, w)
-        self._foreign_fold = (fkey, key, w.untyped_storage(), fold)
-        self._auto_checks_planes(key, fold)
-        return fold
+            def build():
+                n_sat, fv.zeroed_int = fv.zeroed_int, None  # (a rebuild for a new fc_0 gets a fresh counter)
+                fold = ops.fold_build(vols if fv.rows is None else fv.shapes, fv.sparse, w.detach(), rows=fv.rows, n_sat=n_sat)
+                self._auto_checks_planes(fold)
+                return fold
 
-    def _auto_checks_planes(self, key, fold):
+            return fv._memo.get("fold", tkey(w), build)
+
+        # volumes from elsewhere (cloned, loaded, another encoder's): nothing to hang a cache on but the caller's tensors themselves
+        # (not `vols`: those are fresh channels-last views at every call)
+        def build_foreign():
+            sparse = [ops.sparsify(v) for v in vols]
+            counts = torch.cat([sp[2] for sp in sparse]).tolist()  # one read-back: a capacity of every voxel would be ~1 GB of planes
+            sparse = [(g, lin, n, max(int(c), 1)) for (g, lin, n, _), c in zip(sparse, counts)]
+            fold = ops.fold_build(vols, sparse, w.detach())
+            self._auto_checks_planes(fold)
+            return vols, sparse, w, fold
+
+        return self._memo.get("foreign_fold", tkey(w, *feature_volume), build_foreign)[3]
+
+    @property
+    def _foreign_fold(self):
+        """(channels-last views, active sets, fc_0 weight, planes) of the last plain list of volumes, None before the first."""
+        return self._memo.peek("foreign_fold")
+
+    @property
+    def _sat_pending(self):
+        """(counter, event) of a later frame's planes that `check_pending_saturation` has not read yet, or None."""
+        st = self._memo.peek("saturation")
+        return None if st is None else st.get("pending")
+
+    def _saturation(self):
+        """precision 'auto''s record of the current fc_0: 'checked' once the first fold build's saturation count was read,
+        'overflow' once a count was not zero, 'pending' = (counter, event) of a later frame's planes."""
+        return self._memo.get("saturation", tkey(self.fc_0.weight), dict)
+
+    def _auto_checks_planes(self, fold):
         """precision 'auto', once per fc_0 version: read the planes' saturation count (one 4-byte read-back); a non-zero count
         means fc_0 . V left the fp16 range somewhere, and this Network takes the exact kernel from here on (with a warning)."""
         if self.precision != "auto":
             return
-        if self._sat_checked == key:
+        st = self._saturation()
+        if st.get("checked"):
             # a later frame of the same weights: saturation depends on the frame's volumes too, but reading its counter here would
             # drain the launch queue once per frame.  The counter is parked instead and read where the host waits for the device
             # anyway (`check_pending_saturation`, called by Renderer at its per-frame out_sh read-back): a frame whose products
-            # leave the fp16 range is marched clamped ONCE, then 'auto' warns and takes 'f32' for these weights.
-            ev = torch.cuda.Event()
-            ev.record(torch.cuda.current_stream(fold[1][1].device))  # the stream that is building these planes (maybe the prefetch one)
-            self._sat_pending = (key, fold[1][1], ev)
+            # leave the fp16 range is marched clamped ONCE, then 'auto' warns and takes 'f32' for these weights.  (The planes of a
+            # graph capture belong to no pass: nothing is parked.)
+            if not torch.cuda.is_current_stream_capturing():
+                ev = torch.cuda.Event()
+                ev.record(torch.cuda.current_stream(fold[1][1].device))  # the stream that is building these planes (maybe the prefetch one)
+                st["pending"] = (fold[1][1], ev)
             return
-        self._sat_checked = key
-        self._note_saturation(key, int(fold[1][1]))
+        st["checked"] = True
+        self._note_saturation(st, int(fold[1][1]))
 
     def check_pending_saturation(self):
         """Read the saturation counter of the last fold planes built since the previous check (one 4-byte read-back; call it
         where the host synchronises with the device anyway).  Returns the count (0: nothing pending or nothing saturated)."""
-        pend = getattr(self, "_sat_pending", None)
-        if pend is None or self.precision != "auto" or not pend[2].query():  # (planes still being built: look again next time)
+        st = self._memo.peek("saturation")
+        pend = None if st is None else st.get("pending")
+        if pend is None or self.precision != "auto" or not pend[1].query():  # (planes still being built: look again next time)
             return 0
-        self._sat_pending = None
-        n = int(pend[1])
-        self._note_saturation(pend[0], n)
+        st["pending"] = None
+        n = int(pend[0])
+        self._note_saturation(st, n)
         return n
 
-    def _note_saturation(self, key, n):
+    def _note_saturation(self, st, n):
         if n:
             import warnings
 
             warnings.warn("neuralbody_amd: %d products of fc_0 with the latent volumes exceed the fp16 range of the folded planes; "
                           "precision 'auto' takes the exact fp32 kernel for these weights" % n)
-            self._planes_overflow = key
+            st["overflow"] = True
 
     def fold_saturated(self, feature_volume):
         """How many fc_0 . V products of the volumes' folded planes left the fp16 range or are not finite (device -> host read;
         0 for any sane weights: the planes then carry fc_0 . V to fp32 accuracy).  Non-zero: use precision 'f32'."""
-        fv = feature_volume if isinstance(feature_volume, FeatureVolumes) else None
-        fold = fv.fold[2] if fv is not None and fv.fold is not None else (self._foreign_fold[3] if self._foreign_fold else None)
+        fold = feature_volume._memo.peek("fold") if isinstance(feature_volume, FeatureVolumes) else None
+        if fold is None and self._foreign_fold is not None:
+            fold = self._foreign_fold[3]
         return 0 if fold is None else int(fold[1][1])
 
     # ------------------------------------------------------------------ reference API
@@ -648,7 +615,7 @@ class Network(nn.Module):
             scene = self.make_scene(feature_volume, sp_input, prec)
         p = wpts.reshape(-1, 3).float().contiguous()
         v = None if density_only else viewdir.reshape(-1, 3).float().contiguous()
-        lb = None if density_only else self.latent_bias(sp_input["latent_index"])
+        lb = None if density_only else self.latent_bias(sp_input["latent_index"], sp_input.get("_frame_token"))
         packed = self.packed_weights(prec)
         if prec == "f16f6" and p.shape[0] >= self.SORT_MIN_POINTS:
             order = self._spatial_order(p, sp_input)
@@ -714,12 +681,9 @@ class Network(nn.Module):
         if prec != self.march_precision():  # 'auto' just learnt that these weights overflow the folded planes
             prec = self.march_precision()
             scene = self.make_scene(feature_volume, sp_input, prec)
-        lb = self.latent_bias(sp_input["latent_index"])
-        key = (int(n_samples), str(ray_o.device))  # a constant of (S, device), not of the frame
-        t_vals = self._t_vals.get(key)
-        if t_vals is None:
-            t_vals = torch.linspace(0.0, 1.0, steps=int(n_samples)).to(ray_o.device)  # if_clight_renderer.py:13
-            self._t_vals[key] = t_vals
+        lb = self.latent_bias(sp_input["latent_index"], sp_input.get("_frame_token"))
+        t_vals = self._memo.get("t_vals", (int(n_samples), str(ray_o.device)),  # a constant of (S, device), not of the frame
+                                lambda: torch.linspace(0.0, 1.0, steps=int(n_samples)).to(ray_o.device))  # if_clight_renderer.py:13
         ret = ops.march(scene, self.packed_weights(prec), lb, ray_o, ray_d, near, far, t_vals, t_rand,
                         white_bkgd=white_bkgd, want_raw=want_raw, precision=prec, ray_order=ray_order,
                         cull=cull, order_covers_all=order_covers_all, fixup=self.last_sample_fixup)

@@ -14,6 +14,7 @@ import numpy as np
 import torch
 
 from . import ops
+from ._memo import Memo, tkey
 from .parallel import shard_range
 
 
@@ -135,26 +136,17 @@ class NovelViewRenderer:
         self.reuse_volumes = bool(reuse_volumes)
         # render_views: the next view's encoder is enqueued on a second HIP stream before this view's march (Renderer.prefetch)
         self.prefetch_encoder = self.device.type == "cuda" and hasattr(renderer, "prefetch")
-        self._vol_key, self._vols = None, None
+        self._memo = Memo()  # the volumes of the last frame (reuse_volumes)
 
     def _frame_volumes(self, batch):
         if not self.reuse_volumes:
             return None
         net = self.renderer.net
-        coord, out_sh = batch["coord"], batch["out_sh"]
-        # The cache entry HOLDS the tensors it was computed from and compares identity + version counters: a new
-        # frame's `coord` is a different tensor object even when the allocator hands it the old one's address
-        # (round 1 keyed on data_ptr, which a freed-and-reallocated batch reproduces).
-        params = list(net.xyzc_net.parameters()) + [net.c.weight]
-        src = (coord, out_sh, net.training, params)
-        ver = (coord._version, out_sh._version, tuple(p._version for p in params))
-        old = self._vol_key
-        same = old is not None and old[0][0] is coord and old[0][1] is out_sh and old[0][2] == net.training and \
-            len(old[0][3]) == len(params) and all(a is b for a, b in zip(old[0][3], params)) and old[1] == ver
-        if not same:
-            self._vols = net.encode_sparse_voxels(self.renderer.prepare_sp_input(batch))
-            self._vol_key = (src, ver)
-        return self._vols
+        # kept per (coord, out_sh, frame token, BatchNorm mode, encoder parameters): a new frame's `coord` is a different tensor
+        # object even when the allocator hands it the old one's address (round 1 keyed on data_ptr, which a freed-and-reallocated
+        # batch reproduces)
+        key = (tkey(batch["coord"], batch["out_sh"], net.c.weight, *net.xyzc_net.parameters()), batch.get("frame_token"), net.training)
+        return self._memo.get("volumes", key, lambda: net.encode_sparse_voxels(self.renderer.prepare_sp_input(batch)))
 
     def _launch_rays(self, K, RT, can_bounds):
         """nb_raygen of one view + an asynchronous 4-byte copy of its ray count into pinned host memory; the event marks the

@@ -13,6 +13,8 @@ what saturates a 153 GB/s xGMI link, so a single fused all-gather per image is t
 import torch
 import torch.distributed as dist
 
+from ._memo import tkey
+
 
 def shard_range(n, rank, world):
     """Contiguous, balanced [begin, end) of `n` rays for `rank` (sizes differ by at most one; ranges tile
@@ -141,18 +143,13 @@ def shard_ranges(renderer, batch, world):
     if H and W and mask is not None and mask.numel() == int(H) * int(W) and n >= 1:
         if n == int(H) * int(W):
             return shard_ranges_tiled(n, world, H, W, None)
-        # one read-back of the per-band ray counts per mask: kept on the renderer with the mask tensor itself (identity +
-        # version + the caller's frame token, like Renderer._tile_order: the entry holds the tensor, its address cannot be recycled)
-        key = (mask._version, int(world), int(H), int(W), batch.get("frame_token"))
-        c = getattr(renderer, "_shard_cache", None)
-        if c is not None and c[0] is mask and c[1] == key:
-            return list(c[2])
-        ranges = shard_ranges_tiled(n, world, H, W, mask.reshape(-1))
-        try:
-            renderer._shard_cache = (mask, key, ranges)
-        except AttributeError:  # a renderer that takes no attributes
-            pass
-        return list(ranges)
+        # one read-back of the per-band ray counts per (mask tensor, ray count, frame token), kept in the renderer's memo if it
+        # has one (Renderer)
+        memo = getattr(renderer, "_memo", None)
+        build = lambda: shard_ranges_tiled(n, world, H, W, mask.reshape(-1))  # noqa: E731
+        if memo is None:
+            return build()
+        return list(memo.get("shard_ranges", (tkey(mask), int(n), int(world), int(H), int(W), batch.get("frame_token")), build))
     return [shard_range(n, r, world) for r in range(world)]
 
 

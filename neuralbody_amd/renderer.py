@@ -12,6 +12,7 @@ nb_composite) is what a subclass that culls samples would call; render() itself 
 import torch
 
 from . import ops
+from ._memo import Memo, tkey
 
 
 class RenderConfig:
@@ -47,6 +48,8 @@ class Renderer:
     def __init__(self, net, cfg=None):
         self.net = net
         self.cfg = cfg if cfg is not None else RenderConfig()
+        # host-side caches: the batch-index column, out_sh read-backs, tile orders, shard ranges, encoder graphs
+        self._memo = Memo(order_full=8)
 
     # -- if_clight_renderer.py:11-27 (host-visible sampling; the fused path does this in-kernel)
     def get_sampling_points(self, ray_o, ray_d, near, far, t_rand=None):
@@ -74,15 +77,15 @@ class Renderer:
         if sh[0] == 1:
             # batch size 1 (every shipped config): the batch-index column is a constant, kept per (length, dtype, device); the
             # encoder takes the [n, 3] coordinates themselves (`_coord_dhw`) instead of cutting the column off again
-            zc = getattr(self, "_zero_col", None)
-            if zc is None or zc.shape[0] != sh[1] or zc.dtype != coord.dtype or zc.device != coord.device:
-                zc = self._zero_col = torch.zeros((sh[1], 1), dtype=coord.dtype, device=coord.device)
+            zc = self._memo.get("zero_col", (sh[1], coord.dtype, coord.device),
+                                lambda: torch.zeros((sh[1], 1), dtype=coord.dtype, device=coord.device))
             sp_input["_coord_parts"] = (zc, coord)  # 'coord' itself: SpInput.__missing__, on first use
             sp_input["_coord_dhw"] = coord
         else:
             idx = [torch.full([sh[1]], i, dtype=coord.dtype, device=coord.device) for i in range(sh[0])]
             sp_input["coord"] = torch.cat([torch.cat(idx)[:, None], coord], dim=1)
-        sp_input["out_sh"] = self._host_out_sh(batch["out_sh"])
+        sp_input["_frame_token"] = batch.get("frame_token")  # (part of the keys of Network's per-frame caches)
+        sp_input["out_sh"] = self._host_out_sh(batch["out_sh"], sp_input["_frame_token"])
         sp_input["batch_size"] = sh[0]
         sp_input["bounds"] = batch["bounds"]
         sp_input["R"] = batch["R"]
@@ -90,25 +93,21 @@ class Renderer:
         sp_input["latent_index"] = batch["latent_index"]
         return sp_input
 
-    def _host_out_sh(self, t):
+    def _host_out_sh(self, t, frame_token=None):
         """max over the batch of out_sh as a host list (if_clight_renderer.py:40-41: one device -> host sync per render() when
-        the tensor lives on the device).  The last answer is kept together with the tensor OBJECT it was read from (identity
-        and version, the entry holds the tensor so its address cannot be recycled): a caller that renders many views of one
-        frame from the same batch tensors does not stall the launch queue on every view; a DataLoader loop, which makes fresh
-        tensors per frame, syncs once per frame like the reference."""
-        c = getattr(self, "_out_sh_cache", None)
-        token = getattr(self, "_frame_token", None)  # set by render(): a caller that rewrites out_sh in place through a raw pointer
-        if c is not None and c[0] is t and c[1] == (t._version, token):
-            return list(c[2])
-        out_sh, _ = torch.max(t, dim=0)
-        val = out_sh.tolist()
-        # the host has just waited for the device: the moment to look at the previous frame's fold-plane saturation counter
-        # (precision 'auto'; Network._auto_checks_planes parks it instead of draining the queue once per frame)
-        chk = getattr(self.net, "check_pending_saturation", None)
-        if chk is not None and t.is_cuda:
-            chk()
-        self._out_sh_cache = (t, (t._version, token), val)
-        return list(val)
+        the tensor lives on the device).  The last answer is kept per (tensor, frame token): a caller that renders many views of
+        one frame from the same batch tensors does not stall the launch queue on every view; a DataLoader loop, which makes
+        fresh tensors per frame, syncs once per frame like the reference."""
+        def read():
+            val = torch.max(t, dim=0)[0].tolist()
+            # the host has just waited for the device: the moment to look at the previous frame's fold-plane saturation counter
+            # (precision 'auto'; Network._auto_checks_planes parks it instead of draining the queue once per frame)
+            chk = getattr(self.net, "check_pending_saturation", None)
+            if chk is not None and t.is_cuda:
+                chk()
+            return val
+
+        return list(self._memo.get("out_sh", (tkey(t), frame_token), read))
 
     # -- if_clight_renderer.py:54-60
     def get_density_color(self, wpts, viewdir, raw_decoder):
@@ -173,7 +172,6 @@ class Renderer:
             ret = training.render_train(self, batch, t_rand, raw_noise)
             self._mark_inline_encode(ray_o.device)
             return ret
-        self._frame_token = batch.get("frame_token")
         ahead = self._take_prefetched(batch, prefetched) if feature_volume is None else None
         if ahead is not None:
             sp_input, feature_volume = ahead
@@ -277,17 +275,17 @@ class Renderer:
             # ... and never beside an encoder pass that a render() ran inline on the main stream (first view of a loop, a ticket
             # that did not match, a training step): both would update the BatchNorm running statistics in place
             side.wait_event(inl)
-        self._frame_token = batch.get("frame_token")
+        frame_key = self._frame_key(batch)
         with torch.cuda.stream(side):
             sp_input = self.prepare_sp_input(batch)
-            replayed = self._replay_encoder_graph(batch, sp_input, side) if getattr(self, "use_encoder_graph", False) else None
+            replayed = self._replay_encoder_graph(frame_key, sp_input, side) if getattr(self, "use_encoder_graph", False) else None
             if replayed is not None:
                 sp_input, feature_volume = replayed
             else:
                 feature_volume = self._encode_for_ticket(sp_input)
             ready = torch.cuda.Event()
             ready.record(side)
-        return (self._frame_key(batch), sp_input, feature_volume, ready)
+        return (frame_key, sp_input, feature_volume, ready)
 
     def _encode_for_ticket(self, sp_input):
         feature_volume = self.net.encode_sparse_voxels(sp_input)
@@ -305,29 +303,31 @@ class Renderer:
     # capture; loops over the views of ONE frame — turntables, the strong split — reuse it) and on the parameters' versions.
     ENCODER_GRAPH_SLOTS = 2
 
-    def _encoder_graph_key(self, batch):
-        net = self.net
-        return (self._frame_key(batch), bool(net.training), net.march_precision(),
-                tuple((p.data_ptr(), p._version) for p in net.parameters()))
+    @property
+    def _enc_graphs(self):
+        """The captured passes of the current key ({'seen', 'slots', 'turn'}), None before the first; assigning None drops them."""
+        return self._memo.peek("encoder_graph")
 
-    def _replay_encoder_graph(self, batch, sp_input, side):
+    @_enc_graphs.setter
+    def _enc_graphs(self, value):
+        assert value is None, "the captured passes can only be dropped"
+        self._memo.clear("encoder_graph")
+
+    def _replay_encoder_graph(self, frame_key, sp_input, side):
         """(sp_input, feature_volume) of the frame from a captured pass, or None (the caller then enqueues the pass launch by launch:
         the first pass of a frame warms the caches — packed weights, the out_sh read-back, 'auto''s one-time checks — that must not
         sit inside a capture; the next two are the captures themselves, each behind a device synchronisation)."""
-        st = getattr(self, "_enc_graphs", None)
-        key = self._encoder_graph_key(batch)
-        if st is None or not self._same_graph_key(st["key"], key):
-            st = self._enc_graphs = {"key": key, "seen": 0, "slots": [], "turn": 0}
+        net = self.net
+        key = (frame_key, bool(net.training), net.march_precision(), tkey(*net.parameters()))
+        st = self._memo.get("encoder_graph", key, lambda: {"seen": 0, "slots": [], "turn": 0})
         st["seen"] += 1
         if st["seen"] <= 1:
             return None
         if len(st["slots"]) < self.ENCODER_GRAPH_SLOTS:
             g = torch.cuda.CUDAGraph()
             sp = type(sp_input)(sp_input)
-            pend = getattr(self.net, "_sat_pending", None)
             with torch.cuda.graph(g, stream=side):
                 fv = self._encode_for_ticket(sp)
-            self.net._sat_pending = pend  # (a counter parked during capture belongs to no pass)
             st["slots"].append((g, sp, fv))
             g.replay()  # capture records, it does not run
             return sp, fv
@@ -336,14 +336,9 @@ class Renderer:
         g.replay()
         return sp, fv
 
-    @staticmethod
-    def _same_graph_key(a, b):
-        fa, fb = a[0], b[0]
-        return (len(fa) == len(fb) and all((x[0] is y[0] and x[1] == y[1]) if isinstance(x, tuple) else x == y for x, y in zip(fa, fb))
-                and a[1:] == b[1:])
-
     def _frame_key(self, batch):
-        return tuple((batch[k], batch[k]._version) for k in self._FRAME_KEYS) + (batch.get("frame_token"),)
+        """The frame tensors (identity, version) and the caller's frame token: what a ticket and an encoder graph belong to."""
+        return tkey(*(batch[k] for k in self._FRAME_KEYS)), batch.get("frame_token")
 
     def _queue_behind_prefetch(self, device):
         """An encoder pass on the current stream: a prefetched pass may be in flight on the second stream, and two passes at
@@ -368,8 +363,7 @@ class Renderer:
 
     def _ticket_is_for(self, ticket, batch):
         """The ticket's frame tensors are the batch's: the same objects at the same version counters, the same frame token."""
-        key = self._frame_key(batch)
-        return all(a[0] is b[0] and a[1] == b[1] for a, b in zip(ticket[0][:-1], key[:-1])) and ticket[0][-1] == key[-1]
+        return ticket[0] == self._frame_key(batch)
 
     def _take_prefetched(self, batch, ticket):
         if ticket is None or any(k not in batch for k in self._FRAME_KEYS):
@@ -400,32 +394,15 @@ class Renderer:
         if not H or not W or mask is None or mask.numel() != int(H) * int(W) or e <= b:
             return None
         H, W, dev = int(H), int(W), mask.device
-        geo = getattr(self, "_slot_pixels", None)
-        if geo is None or geo[0] != (H, W, str(dev)):
-            geo = self._slot_pixels = ((H, W, str(dev)), ops.tile_pixels(H, W, dev))
+        pixels = self._memo.get("slot_pixels", (H, W, str(dev)), lambda: ops.tile_pixels(H, W, dev))
         if n_pixel == H * W:
-            # every pixel of the image is a ray: the list depends on the image geometry and the ray range only
-            full = getattr(self, "_order_full", None)
-            if full is None:
-                full = self._order_full = {}
-            key = (H, W, b, e, str(dev))
-            if key not in full:
-                while len(full) >= 8:  # a handful of geometries / ray ranges per process; callers that vary them must not grow it
-                    full.pop(next(iter(full)))
-                full[key] = ops.tile_slots(torch.ones(H * W, dtype=torch.bool, device=dev), geo[1], b, e)
-            else:
-                full[key] = full.pop(key)  # most recently used last
-            return full[key]
-        # cached on the mask tensor's IDENTITY: the entry holds the tensor itself, so its address cannot be recycled for
-        # another frame's mask while the entry lives.  A caller that rewrites the same tensor in place through a raw pointer
-        # (nb_raygen) bumps nothing, so the frame token `batch.get("frame_token")` is part of the key when given.
-        cached = getattr(self, "_order_cache", None)
-        token = batch.get("frame_token")
-        if cached is not None and cached[0] is mask and cached[1] == (mask._version, W, b, e, token):
-            return cached[2]
-        order = ops.tile_slots(mask, geo[1], b, e)  # the ray count is whatever the mask holds: no read-back
-        self._order_cache = (mask, (mask._version, W, b, e, token), order)
-        return order
+            # every pixel of the image is a ray: the list depends on the image geometry and the ray range only (a handful of those
+            # per process: the slot keeps the last 8)
+            return self._memo.get("order_full", (H, W, b, e, str(dev)),
+                                  lambda: ops.tile_slots(torch.ones(H * W, dtype=torch.bool, device=dev), pixels, b, e))
+        # kept per mask tensor and frame token (a caller that rewrites the mask in place through a raw pointer, nb_raygen, bumps
+        # no version); the ray count is whatever the mask holds: no read-back
+        return self._memo.get("order", (tkey(mask), W, b, e, batch.get("frame_token")), lambda: ops.tile_slots(mask, pixels, b, e))
 
 
 class RendererMmsk(Renderer):

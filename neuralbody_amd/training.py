@@ -225,7 +225,7 @@ class RenderFunction(torch.autograd.Function):
             w = wpts.reshape(-1, 3).float().contiguous()
             v = viewdir[:, :, None].expand(n_batch, n_pixel, S, 3).reshape(-1, 3).float().contiguous()
             scene = net.make_scene(vols, sp_input)
-            lb = net.latent_bias(sp_input["latent_index"])
+            lb = net.latent_bias(sp_input["latent_index"], sp_input.get("_frame_token"))
             raw, tap = ops.decode_points(scene, net.packed_weights("f32"), lb, w, v, debug=True, precision="f32")
             if raw_noise is not None:
                 # raw2outputs adds randn * raw_noise_std to the densities in front of the relu (nerf_net_utils.py:31-35): the noisy

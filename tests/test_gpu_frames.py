@@ -63,6 +63,27 @@ def test_fresh_batch_per_frame_never_sees_the_previous_pose(precision):
     assert max(errs) <= H.RGB_TOL, errs
 
 
+def test_a_pose_rewritten_under_a_new_frame_token_is_marched():
+    """a caller that rewrites R / Th / bounds in place without moving their version counters (a raw-pointer writer) and
+    says so with a new `frame_token` is marched with the new pose, not with the pose block kept for the old token."""
+    from neuralbody_amd.renderer import RenderConfig, Renderer
+
+    sd = syn.make_weights(3, num_train_frame=7)
+    net = H.make_network(sd, DEV, True, H.DEFAULT_PRECISION)
+    rend = Renderer(net, RenderConfig(N_samples=64, perturb=0.0, H=16, W=16))
+    bd = H.device_batch(_frame(0)[1], DEV)
+    moved = bd["Th"] + 0.05
+    with torch.no_grad():
+        old = rend.render(dict(bd, frame_token=0))["rgb_map"].clone()
+        version = bd["Th"]._version
+        bd["Th"].data.copy_(moved)  # through `.data`: the tensor's version counter does not move
+        assert bd["Th"]._version == version
+        got = rend.render(dict(bd, frame_token=1))["rgb_map"].clone()
+        ref = rend.render(dict(bd, Th=moved.clone()))["rgb_map"]  # the new pose in a tensor of its own
+    assert float((old - ref).abs().max()) > 1e-2  # the pose change is visible
+    assert H.same_result(got, ref, "f16f6", tol=2e-5)
+
+
 def test_reuse_volumes_follows_the_frame():
     """NovelViewRenderer(reuse_volumes=True): two views of frame A share one encode; frame B (fresh tensors, same shapes)
     must be re-encoded even if its `coord` lands on frame A's old address."""

@@ -246,3 +246,22 @@ def test_balanced_band_cuts_properties():
         assert sum(sizes) == total and all(sz <= total / world + biggest + 1e-9 for sz in sizes)
 
     check()
+
+
+def test_cached_shard_ranges_still_check_the_ray_count():
+    """the ranges of a partially covered view are kept per mask tensor; a batch with another ray count under the same
+    mask must still be refused, as the uncached path refuses it."""
+    from neuralbody_amd.network import Network
+    from neuralbody_amd.renderer import RenderConfig, Renderer
+
+    H, W = 16, 16
+    rend = Renderer(Network(num_train_frame=3), RenderConfig(N_samples=8, H=H, W=W))
+    mask = torch.zeros(H * W, dtype=torch.bool)
+    mask[40:200] = True
+    n = int(mask.sum())
+    batch = {"ray_o": torch.zeros(1, n, 3), "mask_at_box": mask[None]}
+    first = parallel.shard_ranges(rend, batch, 2)
+    assert first == parallel.shard_ranges_tiled(n, 2, H, W, mask) and rend._memo.peek("shard_ranges") == first
+    assert parallel.shard_ranges(rend, batch, 2) == first
+    with pytest.raises(ValueError, match="the mask holds %d rays, the batch %d" % (n, n - 1)):
+        parallel.shard_ranges(rend, dict(batch, ray_o=torch.zeros(1, n - 1, 3)), 2)

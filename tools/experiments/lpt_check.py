@@ -26,10 +26,9 @@ with torch.no_grad():
               "dense tiles first": torch.argsort(cost, descending=True),
               "dense tiles last": torch.argsort(cost),
               "random": torch.randperm(groups.shape[0], device=dev)}
-    key = next(iter(rend._order_full))
     for rep in range(2):
         for name, perm in orders.items():
-            rend._order_full[key] = groups[perm].reshape(-1).contiguous()
+            rend._memo.peek("order_full").copy_(groups[perm].reshape(-1))  # the cached slot list of this view, reordered
             for _ in range(3):
                 o = rend.render(pose, feature_volume=fv)
             torch.cuda.synchronize()
