@@ -465,6 +465,26 @@ int nb_image_assemble(const uint8_t *mask_at_box, int64_t n_pixels, const float 
                       int64_t n_rays, int white_bkgd, int bgr, float scale, float *img, float *depth, void *scratch,
                       void *stream);
 
+/* ---------------------------------------------------------------------------------
+ * nb_eval_metrics — replaces Evaluator.evaluate of the quality protocol (lib/evaluators/if_nerf.py:47-74: the scatter
+ * at mask_at_box :56-59, mse :65, psnr_metric :15-18) and ssim_metric (:20-45: crop to cv2.boundingRect(mask), then
+ * skimage.measure.compare_ssim(multichannel=True) of scikit-image 0.14.2, requirements.txt:6) for one view, on device:
+ *   mse   mean (pred - gt)^2 over the compacted fp32 rays (differences and squares in fp32, as the reference's arrays; fp64 sum);
+ *         whole_img != 0 (cfg.eval_whole_img): over the whole float64 images, background included
+ *   psnr  -10 log10(mse)  (+inf for mse = 0)
+ *   ssim  per channel, 7 x 7 uniform window, sample covariance, K1 = 0.01, K2 = 0.03 and compare_ssim's data_range = 2 for
+ *         float images; the mean over every window that lies fully inside the crop (the tight box of the non-zero mask
+ *         pixels; the whole image with whole_img), then over the 3 channels.  Moments, S and all sums in fp64.
+ *   mask_at_box dev [H*W] uint8; rgb_pred, rgb_gt dev [n_rays,3] in compacted pixel order (NULL allowed for n_rays = 0).
+ *   Pixels with a zero mask or a compacted index >= n_rays take the background (white_bkgd ? 1 : 0); no image is written.
+ *   out dev [8] fp64 = {mse, psnr, ssim, x, y, w, h, n_windows} (x, y, w, h: the crop box, 0,0,0,0 for an empty mask).
+ *   A crop under 7 pixels on a side (where compare_ssim raises) gives ssim = NaN and n_windows = 0; n_rays = 0 without
+ *   whole_img gives mse = NaN.  Fixed summation order, no floating-point atomics: the same input gives the same bits.
+ *   scratch dev: nb_eval_metrics_scratch_size(H, W) bytes (0 for sizes the call refuses: H, W < 1 or H*W > 2^30). */
+int64_t nb_eval_metrics_scratch_size(int32_t H, int32_t W);
+int nb_eval_metrics(const uint8_t *mask_at_box, int32_t H, int32_t W, const float *rgb_pred, const float *rgb_gt,
+                    int64_t n_rays, int white_bkgd, int whole_img, double *out, void *scratch, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -106,6 +106,8 @@ SIGNATURES = {
     "nb_raygen": (C.c_int, [_I32, _I32, C.c_double * 9, C.c_double * 9, C.c_double * 3, C.c_float * 6, _P, _P, _P,
                             _P, _P, _P, _P, _P]),
     "nb_image_assemble": (C.c_int, [_P, _I64, _P, _P, _I64, C.c_int, C.c_int, C.c_float, _P, _P, _P, _P]),
+    "nb_eval_metrics_scratch_size": (_I64, [_I32, _I32]),
+    "nb_eval_metrics": (C.c_int, [_P, _I32, _I32, _P, _P, _I64, C.c_int, C.c_int, _P, _P, _P]),
 }
 
 _lib = None

@@ -607,6 +607,33 @@ def image_assemble(mask_at_box, rgb_map, depth_map=None, white_bkgd=False, bgr=F
     return img, depth
 
 
+def eval_metrics(mask_at_box, H, W, rgb_pred, rgb_gt, white_bkgd=False, whole_img=False, out=None):
+    """nb_eval_metrics: mask_at_box [H*W] uint8/bool (any shape, flattened), rgb_pred and rgb_gt [n,3] in compacted pixel
+    order -> out, a [8] float64 device tensor {mse, psnr, ssim, x, y, w, h, n_windows} (if_nerf.py:47-74 for one view).
+    Nothing is read back: ssim is NaN where compare_ssim would raise (crop under 7 pixels on a side)."""
+    H, W = int(H), int(W)
+    mask = mask_at_box.reshape(-1)
+    if mask.dtype == torch.bool:
+        mask = mask.to(torch.uint8)
+    _req(mask, torch.uint8, (H * W,), "mask_at_box")
+    _req(rgb_pred, torch.float32, (None, 3), "rgb_pred")
+    _req(rgb_gt, torch.float32, (rgb_pred.shape[0], 3), "rgb_gt")
+    if out is None:
+        out = torch.empty(8, dtype=torch.float64, device=mask.device)
+    _req(out, torch.float64, (8,), "out")
+    if rgb_pred.device != mask.device or rgb_gt.device != mask.device or out.device != mask.device:
+        raise ValueError("mask_at_box, rgb_pred, rgb_gt and out must share one device")
+    n_bytes = int(_lib.lib().nb_eval_metrics_scratch_size(H, W))
+    if n_bytes <= 0:
+        raise ValueError("eval_metrics: unsupported image size %d x %d" % (H, W))
+    scratch = torch.empty(n_bytes, dtype=torch.uint8, device=mask.device)
+    with torch.cuda.device(mask.device):
+        check(_lib.lib().nb_eval_metrics(ptr(mask), H, W, ptr(rgb_pred), ptr(rgb_gt), rgb_pred.shape[0],
+                                         1 if white_bkgd else 0, 1 if whole_img else 0, ptr(out), ptr(scratch), _stream()),
+              "nb_eval_metrics")
+    return out
+
+
 TILE = 8  # rays are marched in 8 x 8 pixel tiles (64 slots = one workgroup of the fused march), made of four 4 x 4 blocks
 
 
