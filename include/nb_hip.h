@@ -485,6 +485,27 @@ int64_t nb_eval_metrics_scratch_size(int32_t H, int32_t W);
 int nb_eval_metrics(const uint8_t *mask_at_box, int32_t H, int32_t W, const float *rgb_pred, const float *rgb_gt,
                     int64_t n_rays, int white_bkgd, int whole_img, double *out, void *scratch, void *stream);
 
+/* ---------------------------------------------------------------------------------
+ * nb_marching_cubes — replaces the mesh extraction of lib/networks/renderer/if_mesh_renderer.py:46-52
+ * (mcubes.marching_cubes(cube, cfg.mesh_th) on the host float64 cube) on device, on the fp32 cube itself.
+ *   cube dev [X,Y,Z] fp32, C-contiguous (RendererMesh.density_cube); dims = {X, Y, Z}; iso: the threshold (cfg.mesh_th).
+ *   A lattice point is inside iff value > iso (equal and NaN are outside).  Case table: csrc/nb_mc_table.h, generated by
+ *   tools/gen_mc_table.py (ambiguous faces decided by the face's four signs alone: no cracks; normals point from inside
+ *   to outside).  Triangle order and ambiguous-case topology are this table's, not PyMCubes'.
+ *   vertices dev [n_vertices,3] fp32 in lattice index units (like PyMCubes): one per lattice edge whose end points differ in
+ *   inside-ness, at p0 + t * axis with t = (iso - v0) / (v1 - v0) evaluated in fp64 and the coordinate rounded once to fp32.
+ *   Order (part of the contract; no atomics, the same input gives the same bits): vertices by (linear C-order index of the
+ *   edge's lower end point, axis 0/1/2); triangles dev [n_triangles,3] int32 vertex indices by (linear C-order index of the
+ *   cell's lower point, place in the table row), corners in table order.
+ *   nb_marching_cubes_count: flags + two exclusive scans; counts dev [2] = {n_vertices, n_triangles}; no synchronisation.
+ *   nb_marching_cubes_emit: same cube, dims, iso and scratch as the count call before it.  Reads the two totals back from the
+ *   scratch (8 bytes, one stream synchronisation) and returns NB_EINVAL, writing nothing, when they exceed vert_cap / tri_cap.
+ *   scratch dev: nb_marching_cubes_scratch_size(dims) bytes; 0 for dims both calls refuse: a side < 2 or 3*X*Y*Z > 2^31 - 1. */
+int64_t nb_marching_cubes_scratch_size(const int32_t dims[3]);
+int nb_marching_cubes_count(const float *cube, const int32_t dims[3], float iso, int32_t *counts, void *scratch, void *stream);
+int nb_marching_cubes_emit(const float *cube, const int32_t dims[3], float iso, float *vertices, int32_t *triangles,
+                           int32_t vert_cap, int32_t tri_cap, void *scratch, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -108,6 +108,9 @@ SIGNATURES = {
     "nb_image_assemble": (C.c_int, [_P, _I64, _P, _P, _I64, C.c_int, C.c_int, C.c_float, _P, _P, _P, _P]),
     "nb_eval_metrics_scratch_size": (_I64, [_I32, _I32]),
     "nb_eval_metrics": (C.c_int, [_P, _I32, _I32, _P, _P, _I64, C.c_int, C.c_int, _P, _P, _P]),
+    "nb_marching_cubes_scratch_size": (_I64, [_I32x3]),
+    "nb_marching_cubes_count": (C.c_int, [_P, _I32x3, C.c_float, _P, _P, _P]),
+    "nb_marching_cubes_emit": (C.c_int, [_P, _I32x3, C.c_float, _P, _P, _I32, _I32, _P, _P]),
 }
 
 _lib = None

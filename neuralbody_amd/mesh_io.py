@@ -1,0 +1,54 @@
+"""`MeshEvaluator` and `MeshVisualizer` — drop-ins for zju3dv/neuralbody lib/evaluators/if_nerf_mesh.py::Evaluator and
+lib/visualizers/if_nerf_mesh.py::Visualizer (`run.py --type evaluate` / `--type visualize` with the `mesh_cfg` overlay): they
+consume the `{"cube", "mesh"}` dict of RendererMesh.render.  plugins/if_nerf_mesh.py binds them to the reference's cfg."""
+import os
+
+import numpy as np
+import torch
+
+PAD = 10  # the np.pad of if_mesh_renderer.py:46 that both consumers slice off again
+
+
+def _scalar(v):
+    return int(v.reshape(-1)[0].item()) if isinstance(v, torch.Tensor) else int(np.asarray(v).reshape(-1)[0])
+
+
+def occupied_points(cube, pts, mesh_th, pad=PAD):
+    """lib/evaluators/if_nerf_mesh.py:8-12: pts[cube[pad:-pad, pad:-pad, pad:-pad] > mesh_th] as a host array.  `cube` is the
+    float64 ndarray of render() or the device cube of density_cube(); in the second case the selection runs on the device and
+    only the selected points are downloaded."""
+    if isinstance(cube, torch.Tensor) and cube.is_cuda:
+        sel = cube[pad:-pad, pad:-pad, pad:-pad] > mesh_th
+        return pts.detach().to(cube.device)[sel].cpu().numpy()
+    cube = np.asarray(cube.detach().cpu() if isinstance(cube, torch.Tensor) else cube)[pad:-pad, pad:-pad, pad:-pad]
+    pts = pts.detach().cpu().numpy() if isinstance(pts, torch.Tensor) else np.asarray(pts)
+    return pts[cube > mesh_th]
+
+
+class MeshEvaluator:
+    def __init__(self, cfg):
+        self.cfg = cfg  # mesh_th, result_dir
+
+    def evaluate(self, output, batch):
+        pts = occupied_points(output["cube"], batch["pts"][0], float(self.cfg.mesh_th))
+        result_dir = os.path.join(self.cfg.result_dir, "pts")
+        os.makedirs(result_dir, exist_ok=True)
+        result_path = os.path.join(result_dir, "{}.npy".format(_scalar(batch["i"])))
+        np.save(result_path, pts)
+        return result_path
+
+    def summarize(self):
+        return {}
+
+
+class MeshVisualizer:
+    def __init__(self, cfg):
+        self.cfg = cfg  # result_dir
+        print("the results are saved at {}".format(os.path.join(cfg.result_dir, "mesh")))
+
+    def visualize(self, output, batch):
+        result_dir = os.path.join(self.cfg.result_dir, "mesh")
+        os.makedirs(result_dir, exist_ok=True)
+        result_path = os.path.join(result_dir, "{:04d}.ply".format(_scalar(batch["frame_index"])))
+        output["mesh"].export(result_path)
+        return result_path

@@ -634,6 +634,51 @@ def eval_metrics(mask_at_box, H, W, rgb_pred, rgb_gt, white_bkgd=False, whole_im
     return out
 
 
+def marching_cubes_scratch(shape, device):
+    """Scratch of nb_marching_cubes_count / _emit for an [X,Y,Z] cube; ValueError for shapes the calls refuse."""
+    n_bytes = int(_lib.lib().nb_marching_cubes_scratch_size(_i3(shape))) if len(shape) == 3 else 0
+    if n_bytes <= 0:
+        raise ValueError("marching_cubes: unsupported cube shape %s (every side >= 2, 3*X*Y*Z <= 2^31 - 1)" % (tuple(shape),))
+    return torch.empty(n_bytes, dtype=torch.uint8, device=device)
+
+
+def marching_cubes_count(cube, iso, scratch, counts=None):
+    """nb_marching_cubes_count: -> counts, a [2] int32 device tensor {n_vertices, n_triangles}; nothing is read back."""
+    _req(cube, torch.float32, (None, None, None), "cube")
+    if counts is None:
+        counts = torch.empty(2, dtype=torch.int32, device=cube.device)
+    _req(counts, torch.int32, (2,), "counts")
+    with torch.cuda.device(cube.device):
+        check(_lib.lib().nb_marching_cubes_count(ptr(cube), _i3(cube.shape), float(iso), ptr(counts), ptr(scratch), _stream()),
+              "nb_marching_cubes_count")
+    return counts
+
+
+def marching_cubes_emit(cube, iso, scratch, vertices, triangles):
+    """nb_marching_cubes_emit into caller-owned buffers (vertices [Vcap,3] float32, triangles [Tcap,3] int32) after
+    marching_cubes_count on the same cube, iso and scratch.  Raises NbError, with the buffers untouched, when they are too small."""
+    _req(cube, torch.float32, (None, None, None), "cube")
+    _req(vertices, torch.float32, (None, 3), "vertices")
+    _req(triangles, torch.int32, (None, 3), "triangles")
+    with torch.cuda.device(cube.device):
+        check(_lib.lib().nb_marching_cubes_emit(ptr(cube), _i3(cube.shape), float(iso), ptr(vertices), ptr(triangles),
+                                                vertices.shape[0], triangles.shape[0], ptr(scratch), _stream()),
+              "nb_marching_cubes_emit")
+    return vertices, triangles
+
+
+def marching_cubes(cube, iso):
+    """Marching cubes of a device fp32 cube [X,Y,Z] (if_mesh_renderer.py:46-52 without the host): -> (vertices [V,3] float32 in
+    lattice index units, triangles [T,3] int32), device tensors of the exact size, in the order include/nb_hip.h states.
+    Count, ONE host read of the two counts, allocate, emit."""
+    _req(cube, torch.float32, (None, None, None), "cube")
+    scratch = marching_cubes_scratch(cube.shape, cube.device)
+    n_vert, n_tri = (int(v) for v in marching_cubes_count(cube, iso, scratch).tolist())
+    vertices = torch.empty((n_vert, 3), dtype=torch.float32, device=cube.device)
+    triangles = torch.empty((n_tri, 3), dtype=torch.int32, device=cube.device)
+    return marching_cubes_emit(cube, iso, scratch, vertices, triangles)
+
+
 TILE = 8  # rays are marched in 8 x 8 pixel tiles (64 slots = one workgroup of the fused march), made of four 4 x 4 blocks
 
 

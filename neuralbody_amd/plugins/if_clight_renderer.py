@@ -23,6 +23,7 @@ class _LiveCfg:
     H = property(lambda self: int(cfg.H * cfg.ratio))  # image_rays geometry, lib/utils/render_utils.py:121-122
     W = property(lambda self: int(cfg.W * cfg.ratio))
     mesh_th = property(lambda self: float(cfg.mesh_th))
+    mesh_backend = property(lambda self: str(getattr(cfg, "mesh_backend", "auto")))  # not a reference key: "auto" unless set
 
 
 class Renderer(_Renderer):

@@ -18,7 +18,8 @@ from ._memo import Memo, tkey
 class RenderConfig:
     """The cfg keys the hot path reads."""
 
-    def __init__(self, N_samples=64, perturb=0.0, raw_noise_std=0.0, white_bkgd=False, H=None, W=None, mesh_th=50.0):
+    def __init__(self, N_samples=64, perturb=0.0, raw_noise_std=0.0, white_bkgd=False, H=None, W=None, mesh_th=50.0,
+                 mesh_backend="auto"):
         # H, W (optional): image size of the view the rays come from (cfg.H * cfg.ratio in the reference); when
         # batch['mask_at_box'] covers H*W pixels, rays are marched in 8x8 pixel tiles
         self.H, self.W = H, W
@@ -27,6 +28,9 @@ class RenderConfig:
         self.raw_noise_std = float(raw_noise_std)
         self.white_bkgd = bool(white_bkgd)
         self.mesh_th = float(mesh_th)  # lib/config/config.py:45; the shipped configs override it to 5
+        # RendererMesh.render: "auto" = PyMCubes on the host when it imports, else marching cubes on the device; "device" = always
+        # on the device (not a reference key)
+        self.mesh_backend = str(mesh_backend)
 
 
 class SpInput(dict):
@@ -429,15 +433,19 @@ class RendererMsk(Renderer):
 
 class RendererMesh(Renderer):
     """lib/networks/renderer/if_mesh_renderer.py::Renderer — density on the lattice of
-    multi_view_mesh_dataset.py:142-158 for mesh extraction.  The hot part (encoder + `calculate_density` of every
+    multi_view_mesh_dataset.py:142-158 and the mesh of its iso-surface.  The hot part (encoder + `calculate_density` of every
     lattice point flagged `inside`) runs on HIP in ONE nb_decode_points launch (the reference chunks 131 072 points per
-    call, :37); marching cubes is CPU post-processing of the reference's own dependencies (PyMCubes, trimesh)."""
+    call, :37).  Marching cubes (:46-52) runs on the device too (`extract_mesh`: nb_marching_cubes on the fp32 cube, which is
+    never downloaded); `render` keeps the reference's host post-processing (PyMCubes, trimesh) wherever PyMCubes imports and
+    cfg.mesh_backend does not say "device"."""
+
+    PAD = 10  # np.pad(cube, 10), if_mesh_renderer.py:46
 
     def batchify_rays(self, wpts, alpha_decoder, chunk=1024 * 32):
         """if_mesh_renderer.py:15-24; kept for subclasses — chunking is not needed for memory here."""
         return torch.cat([alpha_decoder(wpts[:, i:i + chunk]) for i in range(0, wpts.shape[1], chunk)], 1)
 
-    def density_cube(self, batch, pad=10):
+    def density_cube(self, batch, pad=PAD):
         """-> DEVICE float32 tensor [X+2*pad, Y+2*pad, Z+2*pad]: alpha at the inside lattice points, 0 elsewhere."""
         pts = batch["pts"]
         inside = batch["inside"][0].bool()
@@ -449,10 +457,47 @@ class RendererMesh(Renderer):
         cube[inside] = alpha[0, :, 0]
         return torch.nn.functional.pad(cube, (pad,) * 6)
 
-    def render(self, batch):
-        import mcubes  # CPU marching cubes, as in the reference (if_mesh_renderer.py:6,46)
-        import trimesh
+    def _to_world(self, vertices, batch, pad=PAD):
+        """Lattice index units of the padded cube -> world units: (v - pad) * step + wbounds[0] (the two lines the reference
+        leaves commented out, if_mesh_renderer.py:49-50, with the step read from the lattice instead of the literal 0.005)."""
+        pts = batch["pts"]
+        step = torch.stack([pts[0, 1, 0, 0, 0] - pts[0, 0, 0, 0, 0], pts[0, 0, 1, 0, 1] - pts[0, 0, 0, 0, 1],
+                            pts[0, 0, 0, 1, 2] - pts[0, 0, 0, 0, 2]]).to(vertices)
+        return (vertices - float(pad)) * step + batch["wbounds"][0, 0].to(vertices)
 
-        cube = self.density_cube(batch).double().cpu().numpy()
-        vertices, triangles = mcubes.marching_cubes(cube, self.cfg.mesh_th)
+    def extract_mesh(self, batch, world=False, cube=None):
+        """-> DEVICE (vertices [V,3] float32, triangles [T,3] int32) of the iso-surface cube == cfg.mesh_th (ops.marching_cubes;
+        the cube stays on the device).  Vertices in index units of the padded cube like PyMCubes', or in world units."""
+        if cube is None:
+            cube = self.density_cube(batch)
+        vertices, triangles = ops.marching_cubes(cube.contiguous(), self.cfg.mesh_th)
+        return (self._to_world(vertices, batch) if world else vertices), triangles
+
+    def render(self, batch):
+        backend = getattr(self.cfg, "mesh_backend", "auto")
+        if backend not in ("auto", "device"):
+            raise ValueError("mesh_backend must be 'auto' or 'device', got %r" % (backend,))
+        mcubes = None
+        if backend == "auto":
+            try:
+                import mcubes  # CPU marching cubes, as in the reference (if_mesh_renderer.py:6,46)
+            except ImportError:
+                mcubes = None
+        if mcubes is not None:
+            import trimesh
+
+            cube = self.density_cube(batch).double().cpu().numpy()
+            vertices, triangles = mcubes.marching_cubes(cube, self.cfg.mesh_th)
+            return {"cube": cube, "mesh": trimesh.Trimesh(vertices, triangles)}
+
+        cube_dev = self.density_cube(batch)
+        vertices, triangles = self.extract_mesh(batch, cube=cube_dev)
+        cube = cube_dev.double().cpu().numpy()  # the float64 ndarray the reference's evaluator slices
+        vertices, triangles = vertices.double().cpu().numpy(), triangles.cpu().numpy()
+        try:
+            import trimesh
+        except ImportError:
+            from .mesh import TriMesh
+
+            return {"cube": cube, "mesh": TriMesh(vertices, triangles)}
         return {"cube": cube, "mesh": trimesh.Trimesh(vertices, triangles)}
