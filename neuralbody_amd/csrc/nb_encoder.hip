@@ -24,18 +24,9 @@
 #include "nb_scan.h"
 #include "nb_scan_dev.h"
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-#define NB_MFMA(a, b, c) __builtin_amdgcn_mfma_f32_32x32x2f32((a), (b), (c), 0, 0, 0)
+#include "nb_enc_tile.h"
 
 namespace {
-
-struct Dims {
-    int d, h, w;
-};
-
-__host__ __device__ constexpr int tile_row(int r, int hi) { return (r & 3) + 8 * (r >> 2) + 4 * hi; }
 
 // ------------------------------------------------------------------ voxelisation
 __global__ void vox_scatter_kernel(const int *__restrict__ coord, int n, Dims g, int *__restrict__ grid) {
@@ -224,64 +215,6 @@ __global__ __launch_bounds__(nbscan::BLOCK) void grid_number_all_kernel(DownAll 
     if ((int)blockIdx.x == a.tile0[l + 1] - 1 && threadIdx.x == 0) *a.n_out[l] = min(before + tot, cap);
 }
 
-// Row of the input level under kernel offset o of output voxel (z, y, x), or -1.  stride > 0: the forward gather, input voxel
-// = stride * out - 1 + k.  stride < 0: the TRANSPOSED gather of a layer of stride -stride (its backward-input product as a convolution
-// of its own, offsets already mirrored by nb_enc_conv_pack16 mode 1): "input" voxel = (out - 1 + k) / -stride where that divides.
-__device__ __forceinline__ int neighbour_row(const int *__restrict__ in_grid, Dims gi, int z, int y, int x, int o, int stride, bool valid) {
-    const int kd = o / 9, kh = (o / 3) % 3, kw = o % 3;
-    const int mul = stride > 0 ? stride : 1, low = stride > 0 ? 0 : -stride - 1, sh = stride > 0 ? 0 : (-stride) >> 1;  // -stride in {1, 2}
-    int iz = z * mul - 1 + kd, iy = y * mul - 1 + kh, ix = x * mul - 1 + kw;
-    if (!valid || ((iz | iy | ix) & low) != 0 || iz < 0 || iy < 0 || ix < 0) return -1;
-    iz >>= sh, iy >>= sh, ix >>= sh;
-    if (iz >= gi.d || iy >= gi.h || ix >= gi.w) return -1;
-    return in_grid[((long long)iz * gi.h + iy) * gi.w + ix];
-}
-
-// ------------------------------------------------------------------ a tile's way out
-// The tile is stored; its BatchNorm sums (fp64: sum and sum of squares per channel) meet those of the workgroup's other waves in LDS
-// and leave as ONE atomic per channel and workgroup.  As one pair of atomics per WAVE the ~900 waves of a 29 k-row level queued on
-// the layer's 2 COUT addresses: 14 of the 52 us of a 64 -> 64 launch (profiles/r05_conv_stamps.log).  Every wave of the workgroup
-// calls this (a wave without rows brings zeros; `active` false: a wave beyond the NW that hold tiles, for the barrier only); `red`: NW * NT * 64
-// doubles of LDS that nobody reads or writes any more.
-template <int COUT, int NT, int NW>
-__device__ __forceinline__ void store_tile_and_sums(const f32x16 (&acc)[NT], int row0, int n, int ct, float *__restrict__ out_rows,
-                                                    double *__restrict__ stats, double *red, int wv, int lane,
-                                                    bool active = true) {
-    const int i = lane & 31, hi = lane >> 5;
-    // D fragment: lane (j = i, hi) holds channel (ct + t) * 32 + j of rows row0 + tile_row(r, hi)
-#pragma unroll
-    for (int t = 0; t < NT; ++t) {
-        if (!active) break;  // (wave-uniform) a wave that only keeps the barrier company
-        const int co = (ct + t) * 32 + i;
-        const bool cok = (COUT % 32 == 0) || co < COUT;
-        double s = 0.0, ss = 0.0;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int orow = row0 + tile_row(r, hi);
-            const float v = acc[t][r];
-            if (orow < n && cok) {
-                out_rows[(size_t)orow * COUT + co] = v;
-                s += (double)v;
-                ss += (double)v * (double)v;
-            }
-        }
-        s += __shfl_xor(s, 32);
-        ss += __shfl_xor(ss, 32);
-        if (hi == 0) {
-            red[((wv * NT + t) * 2) * 32 + i] = s;
-            red[((wv * NT + t) * 2 + 1) * 32 + i] = ss;
-        }
-    }
-    __syncthreads();
-    if (threadIdx.x < NT * 64) {  // thread = (tile, which sum, channel of the tile)
-        const int t = threadIdx.x >> 6, which = (threadIdx.x >> 5) & 1, co = (ct + t) * 32 + (threadIdx.x & 31);
-        double v = 0.0;
-#pragma unroll
-        for (int w = 0; w < NW; ++w) v += red[((w * NT + t) * 2 + which) * 32 + (threadIdx.x & 31)];
-        if ((COUT % 32 == 0) || co < COUT) atomicAdd(&stats[which * COUT + co], v);
-    }
-}
-
 // ------------------------------------------------------------------ sparse 3x3x3 convolution
 template <int CIN, int COUT>
 __global__ __launch_bounds__(256, 2) void conv_kernel(const float *__restrict__ in_rows, const int *__restrict__ in_grid,
@@ -293,49 +226,26 @@ __global__ __launch_bounds__(256, 2) void conv_kernel(const float *__restrict__ 
     // few rows (1.6 k - 13 k), so splitting Cout across waves is what fills the 1024 SIMDs
     constexpr int NT = 1, HALF = CIN / 2;
     const int ct = blockIdx.y;  // channel tile
-    const int lane = threadIdx.x & 63, i = lane & 31, hi = lane >> 5;
-    const int wave = blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int n = *n_out;
-    const int row0 = wave * 32;
-    if (blockIdx.x * 128 >= n) return;  // workgroup-uniform: the waves of a live workgroup meet at the barrier of the sums
-    const int row = row0 + i;
-    const bool valid = row < n;
-    const int lin = valid ? out_lin[row] : 0;
-    const int x = lin % go.w, y = (lin / go.w) % go.h, z = lin / (go.w * go.h);
+    ConvTile tl;
+    if (!tl.init((blockIdx.x * 4 + (threadIdx.x >> 6)) * 32, blockIdx.x * 128, n_out, out_lin, go)) return;
+    const int i = tl.i, hi = tl.hi;
     f32x16 acc[NT];
 #pragma unroll
-    for (int t = 0; t < NT; ++t)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
+    for (int t = 0; t < NT; ++t) acc[t] = zero_acc();
 
     // all 27 neighbour indices first (independent loads), then the rows of offset o + 1 in flight while offset o multiplies: as a
     // chain of grid lookup -> row load -> MFMA per offset the 16-channel layers ran at 0.7 us per offset for 0.25 us of MFMAs
     int nbrs[27];
-#pragma unroll
-    for (int o = 0; o < 27; ++o) {
-        nbrs[o] = neighbour_row(in_grid, gi, z, y, x, o, stride, valid);
-    }
+    tl.fill_neighbours(nbrs, in_grid, gi, stride);
     f32x4 Ar[2][HALF / 4];
-    auto load_rows = [&](int nbr, f32x4 (&dst)[HALF / 4]) {
-        const f32x4 *p = reinterpret_cast<const f32x4 *>(in_rows + (size_t)(nbr >= 0 ? nbr : 0) * CIN + hi * HALF);
-#pragma unroll
-        for (int q = 0; q < HALF / 4; ++q) dst[q] = p[q];
-    };
-    load_rows(nbrs[0], Ar[0]);
+    load_row_half<CIN>(in_rows, nbrs[0], hi, Ar[0]);
 #pragma unroll
     for (int o = 0; o < 27; ++o) {
-        if (o + 1 < 27) load_rows(nbrs[o + 1], Ar[(o + 1) & 1]);
+        if (o + 1 < 27) load_row_half<CIN>(in_rows, nbrs[o + 1], hi, Ar[(o + 1) & 1]);
         const int nbr = nbrs[o];
         if (!__any(nbr >= 0)) continue;  // nothing active under this offset for the whole tile
         float A[HALF];
-#pragma unroll
-        for (int q = 0; q < HALF / 4; ++q) {
-            const f32x4 v = Ar[o & 1][q];
-            A[4 * q] = nbr >= 0 ? v.x : 0.f;
-            A[4 * q + 1] = nbr >= 0 ? v.y : 0.f;
-            A[4 * q + 2] = nbr >= 0 ? v.z : 0.f;
-            A[4 * q + 3] = nbr >= 0 ? v.w : 0.f;
-        }
+        mask_row_half<CIN>(Ar[o & 1], nbr >= 0, A);
         const float *wo = weight + ((size_t)o * CIN + hi * HALF) * COUT + ct * 32 + i;  // B[k=hi][j=i]
 #pragma unroll
         for (int c = 0; c < HALF; ++c) {
@@ -348,7 +258,7 @@ __global__ __launch_bounds__(256, 2) void conv_kernel(const float *__restrict__ 
         }
     }
     __shared__ double red[4 * NT * 64];
-    store_tile_and_sums<COUT, NT, 4>(acc, row0, n, ct, out_rows, stats, red, threadIdx.x >> 6, lane);
+    store_tile_and_sums<COUT, NT, 4>(acc, tl.row0, tl.n, ct, out_rows, stats, red, threadIdx.x >> 6, tl.lane);
 }
 
 // ------------------------------------------------------------------ the same convolution on the 16-bit matrix pipe
@@ -360,27 +270,11 @@ __global__ __launch_bounds__(256, 2) void conv_kernel(const float *__restrict__ 
 // 17 layers.  The activated rows arrive ALREADY split from the producing BatchNorm kernel (two fp16 planes in the bytes of
 // one fp32 row matrix: [cap, C] heads | [cap, C] remainders), the weights from nb_enc_conv_pack16 in B-fragment order:
 // [offset][K chunk][channel tile][head, remainder][lane] x 8 fp16.
-typedef _Float16 bf16x8 __attribute__((ext_vector_type(8)));  // (the name predates the switch to fp16)
-typedef _Float16 nb_h16;
-// BF: the operands are bf16 head / remainder pairs (the backward-input convolution: gradients span more binades than an
-// un-scaled fp16 head holds; a bf16 pair carries 16 mantissa bits, ~2^-16 relative per product) instead of fp16 pairs
-typedef __bf16 nb_bf16x8 __attribute__((ext_vector_type(8)));
-template <bool BF>
-__device__ __forceinline__ f32x16 nb_mfma16(const bf16x8 a, const bf16x8 b, const f32x16 c) {
-    if constexpr (BF)
-        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(nb_bf16x8, a), __builtin_bit_cast(nb_bf16x8, b), c, 0, 0, 0);
-    else
-        return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
-}
-#define NB_MFMA16(a, b, c) nb_mfma16<BF>((a), (b), (c))
-
 // mode 0: the forward weight [27][cin][cout] as fp16 pairs.  mode 1: the weight of the BACKWARD-INPUT convolution of a stride-1
 // layer — dIn[q] = sum_o dOut[q + (o' - 1)] . W[26 - o']^T, i.e. the same kernels on the mirrored offsets and the transposed
 // slabs — as bf16 pairs: cin / cout are those of the packed convolution (= the layer's cout / cin), w is the layer's weight
-__global__ void conv_pack16_kernel(const float *__restrict__ w, int cin, int cout, bf16x8 *__restrict__ out, int mode) {
-    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;  // (((o * NC + c) * NTT + t) * 2 + part) * 64 + lane
-    const int nc = cin / 16, ntt = cout / 32;
-    if (idx >= (long long)27 * nc * ntt * 2 * 64) return;
+__device__ __forceinline__ bf16x8 pack16_element(const float *__restrict__ w, int cin, int cout, int mode, long long idx) {
+    const int nc = cin / 16, ntt = cout / 32;  // idx = (((o * NC + c) * NTT + t) * 2 + part) * 64 + lane
     const int lane = (int)(idx & 63), part = (int)((idx >> 6) & 1);
     const long long q = idx >> 7;
     const int t = (int)(q % ntt), c = (int)((q / ntt) % nc), o = (int)(q / ((long long)ntt * nc));
@@ -400,10 +294,10 @@ __global__ void conv_pack16_kernel(const float *__restrict__ w, int cin, int cou
             v[e] = __builtin_bit_cast(nb_h16, r);
         }
     }
-    out[idx] = v;
+    return v;
 }
 
-// the same for up to NB_PACK_BATCH_MAX (weight, mode) jobs in one launch: blockIdx.y = the job, blockIdx.x over its elements
+// up to NB_PACK_BATCH_MAX (weight, mode) jobs in one launch: blockIdx.y = the job, blockIdx.x over its elements
 struct PackBatch {
     const float *w[NB_PACK_BATCH_MAX];
     bf16x8 *out[NB_PACK_BATCH_MAX];
@@ -414,30 +308,9 @@ __global__ void conv_pack16_batch_kernel(PackBatch b) {
     const float *__restrict__ w = b.w[job];
     bf16x8 *__restrict__ out = b.out[job];
     const int cin = b.cin[job], cout = b.cout[job], mode = b.mode[job];
-    const int nc = cin / 16, ntt = cout / 32;
-    const long long total = (long long)27 * nc * ntt * 2 * 64;
-    for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long long)gridDim.x * blockDim.x) {
-        const int lane = (int)(idx & 63), part = (int)((idx >> 6) & 1);
-        const long long q = idx >> 7;
-        const int t = (int)(q % ntt), c = (int)((q / ntt) % nc), o = (int)(q / ((long long)ntt * nc));
-        const int j = lane & 31, hi = lane >> 5;
-        bf16x8 v;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            const int k = 16 * c + 8 * hi + e, n = 32 * t + j;
-            if (mode == 0) {
-                const float x = w[((size_t)o * cin + k) * cout + n];
-                const nb_h16 h = (nb_h16)x;
-                v[e] = part ? (nb_h16)(x - (float)h) : h;
-            } else {
-                const float x = w[((size_t)(26 - o) * cout + n) * cin + k];
-                const __bf16 h = (__bf16)x;
-                const __bf16 r = part ? (__bf16)(x - (float)h) : h;
-                v[e] = __builtin_bit_cast(nb_h16, r);
-            }
-        }
-        out[idx] = v;
-    }
+    const long long total = (long long)27 * (cin / 16) * (cout / 32) * 2 * 64;
+    for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long long)gridDim.x * blockDim.x)
+        out[idx] = pack16_element(w, cin, cout, mode, idx);
 }
 
 // one wave = 32 output rows x NT tiles of 32 output channels (blockIdx.y selects the tile group)
@@ -449,51 +322,27 @@ __global__ __launch_bounds__(256, 2) void conv16_kernel(const unsigned short *__
                                                      double *__restrict__ stats) {
     constexpr int NC = CIN / 16, NTT = COUT / 32;
     const int ct = blockIdx.y * NT;
-    const int lane = threadIdx.x & 63, i = lane & 31, hi = lane >> 5;
-    const int wave = blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int n = *n_out;
-    const int row0 = wave * 32;
-    if (blockIdx.x * 128 >= n) return;  // workgroup-uniform: the waves of a live workgroup meet at the barrier of the sums
-    const int row = row0 + i;
-    const bool valid = row < n;
-    const int lin = valid ? out_lin[row] : 0;
-    const int x = lin % go.w, y = (lin / go.w) % go.h, z = lin / (go.w * go.h);
+    ConvTile tl;
+    if (!tl.init((blockIdx.x * 4 + (threadIdx.x >> 6)) * 32, blockIdx.x * 128, n_out, out_lin, go)) return;
+    const int lane = tl.lane, hi = tl.hi;
     f32x16 acc[NT];
 #pragma unroll
-    for (int t = 0; t < NT; ++t)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
+    for (int t = 0; t < NT; ++t) acc[t] = zero_acc();
 
     // The wave has ~1.5 companions per SIMD on the deep levels, so nothing hides a dependent load chain (index -> row ->
     // MFMA) but the wave itself: all 27 neighbour indices are fetched first, and the rows of offset o + 1 while offset o is
     // multiplied (the fp32 kernel above pays ~9 k cycles per offset for what is 0.8 k cycles of MFMA work here).
     int nbrs[27];
-#pragma unroll
-    for (int o = 0; o < 27; ++o) {
-        nbrs[o] = neighbour_row(in_grid, gi, z, y, x, o, stride, valid);
-    }
-    // A fragments: lane (row i, half hi) holds channels 16 c + 8 hi .. + 7 of its neighbour row (zeros when inactive)
-    auto load_rows = [&](int nbr, bf16x8 (&ah)[NC], bf16x8 (&al)[NC]) {
-        const size_t r = (size_t)(nbr >= 0 ? nbr : 0) * CIN + 8 * hi;
-        const bf16x8 *ph = reinterpret_cast<const bf16x8 *>(in_split + r);
-        const bf16x8 *pl = reinterpret_cast<const bf16x8 *>(in_split + in_plane + r);
-#pragma unroll
-        for (int c = 0; c < NC; ++c) {
-            ah[c] = ph[2 * c];
-            al[c] = pl[2 * c];
-        }
-    };
+    tl.fill_neighbours(nbrs, in_grid, gi, stride);
     bf16x8 ah[2][NC], al[2][NC];
-    load_rows(nbrs[0], ah[0], al[0]);
+    load_split_rows<CIN>(in_split, in_plane, nbrs[0], hi, ah[0], al[0]);
 #pragma unroll
     for (int o = 0; o < 27; ++o) {
-        if (o + 1 < 27) load_rows(nbrs[o + 1], ah[(o + 1) & 1], al[(o + 1) & 1]);
+        if (o + 1 < 27) load_split_rows<CIN>(in_split, in_plane, nbrs[o + 1], hi, ah[(o + 1) & 1], al[(o + 1) & 1]);
         const int nbr = nbrs[o];
         if (!__any(nbr >= 0)) continue;  // nothing active under this offset for the whole tile
         const bf16x8 *wo = wp + (((size_t)o * NC * NTT + ct) * 2) * 64 + lane;
-        bf16x8 zero;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) zero[e] = (nb_h16)0.f;
+        const bf16x8 zero = zero_fragment();
 #pragma unroll
         for (int c = 0; c < NC; ++c) {
             const bf16x8 a_h = nbr >= 0 ? ah[o & 1][c] : zero, a_l = nbr >= 0 ? al[o & 1][c] : zero;  // row 0 was read for inactive lanes
@@ -507,7 +356,7 @@ __global__ __launch_bounds__(256, 2) void conv16_kernel(const unsigned short *__
         }
     }
     __shared__ double red[4 * NT * 64];
-    store_tile_and_sums<COUT, NT, 4>(acc, row0, n, ct, out_rows, stats, red, threadIdx.x >> 6, lane);
+    store_tile_and_sums<COUT, NT, 4>(acc, tl.row0, tl.n, ct, out_rows, stats, red, threadIdx.x >> 6, lane);
 }
 
 typedef const void __attribute__((address_space(1))) *nb_gptr_t;
@@ -586,9 +435,8 @@ __device__ __forceinline__ void multiply_offset(f32x16 (&acc)[NT], const bf16x8 
                                                 const bf16x8 *sl, Fetch fetch = Fetch()) {
     static_assert(VPC == 0 || (3 * NT) % VPC == 0, "the chunk's MFMAs split evenly round its fetches");
     constexpr int GROUPS = VPC > 0 ? VPC : 1, PER = 3 * NT / GROUPS;
-    bf16x8 b[2][NT][2], zero;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) zero[e] = (nb_h16)0.f;
+    bf16x8 b[2][NT][2];
+    const bf16x8 zero = zero_fragment();
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
         b[0][t][0] = sl[(t * 2) * 64];
@@ -655,20 +503,13 @@ __global__ __launch_bounds__(256, 2) void conv16_lds_kernel(const unsigned short
     __shared__ __attribute__((aligned(16))) char lds[2 * NFRAG * 1024 + 4 * STAGE_BYTES];
     char (*const slab)[NFRAG * 1024] = reinterpret_cast<char (*)[NFRAG * 1024]>(lds);
     const int ct = blockIdx.y * NT;
-    const int lane = threadIdx.x & 63, i = lane & 31, hi = lane >> 5;
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int n = *n_out;
-    const int row0 = (blockIdx.x * 4 + wv) * 32;
-    if (blockIdx.x * 128 >= n) return;  // workgroup-uniform: every wave of a live workgroup takes part in the barriers
-    const int row = row0 + i;
-    const bool valid = row < n;
-    const int lin = valid ? out_lin[row] : 0;
-    const int x = lin % go.w, y = (lin / go.w) % go.h, z = lin / (go.w * go.h);
+    ConvTile tl;
+    if (!tl.init((blockIdx.x * 4 + wv) * 32, blockIdx.x * 128, n_out, out_lin, go)) return;
+    const int lane = tl.lane, hi = tl.hi;
     f32x16 acc[NT];
 #pragma unroll
-    for (int t = 0; t < NT; ++t)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
+    for (int t = 0; t < NT; ++t) acc[t] = zero_acc();
 
     auto issue_slab_piece = [&](int o, int buf, int q) {  // piece q of this wave's share of offset o's fragments -> slab[buf]
         const int f = wv * PER_WAVE + q;           // local fragment (c, t, part) = ((c * NT) + t) * 2 + part
@@ -681,20 +522,7 @@ __global__ __launch_bounds__(256, 2) void conv16_lds_kernel(const unsigned short
         for (int q = 0; q < PER_WAVE; ++q) issue_slab_piece(o, buf, q);
     };
     int nbrs[27];
-#pragma unroll
-    for (int o = 0; o < 27; ++o) {
-        nbrs[o] = neighbour_row(in_grid, gi, z, y, x, o, stride, valid);
-    }
-    auto load_rows = [&](int nbr, bf16x8 (&ah)[NC], bf16x8 (&al)[NC]) {
-        const size_t r = (size_t)(nbr >= 0 ? nbr : 0) * CIN + 8 * hi;
-        const bf16x8 *ph = reinterpret_cast<const bf16x8 *>(in_split + r);
-        const bf16x8 *pl = reinterpret_cast<const bf16x8 *>(in_split + in_plane + r);
-#pragma unroll
-        for (int c = 0; c < NC; ++c) {
-            ah[c] = ph[2 * c];
-            al[c] = pl[2 * c];
-        }
-    };
+    tl.fill_neighbours(nbrs, in_grid, gi, stride);
     // STAGE: the wave's 32 neighbour rows reach it through its own LDS stage (RowStage), fetched while the previous offset
     // multiplies; else (no room beside the slabs) straight into a second set of fragment registers
     char *const mine = lds + 2 * NFRAG * 1024 + wv * STAGE_BYTES;
@@ -703,7 +531,7 @@ __global__ __launch_bounds__(256, 2) void conv16_lds_kernel(const unsigned short
     bf16x8 ah[NBUF][NC], al[NBUF][NC];
     issue_slab(0, 0);
     if constexpr (STAGE) rs.fetch(in_split, in_plane, nbrs[0], mine);
-    else load_rows(nbrs[0], ah[0], al[0]);
+    else load_split_rows<CIN>(in_split, in_plane, nbrs[0], hi, ah[0], al[0]);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
 #pragma unroll
@@ -738,7 +566,7 @@ __global__ __launch_bounds__(256, 2) void conv16_lds_kernel(const unsigned short
         } else {
             if (o + 1 < 27) {
                 issue_slab(o + 1, (o + 1) & 1);
-                load_rows(nbrs[o + 1], ah[(o + 1) & 1], al[(o + 1) & 1]);
+                load_split_rows<CIN>(in_split, in_plane, nbrs[o + 1], hi, ah[(o + 1) & 1], al[(o + 1) & 1]);
             }
             if (live) multiply_offset<NC, NT, BF>(acc, ah[o & (NBUF - 1)], al[o & (NBUF - 1)], nbr >= 0, sl);
         }
@@ -748,7 +576,7 @@ __global__ __launch_bounds__(256, 2) void conv16_lds_kernel(const unsigned short
         }
     }
     __syncthreads();  // the slabs are dead: their memory takes the sums
-    store_tile_and_sums<COUT, NT, 4>(acc, row0, n, ct, out_rows, stats, reinterpret_cast<double *>(lds), wv, lane);
+    store_tile_and_sums<COUT, NT, 4>(acc, tl.row0, tl.n, ct, out_rows, stats, reinterpret_cast<double *>(lds), wv, lane);
 }
 
 // The same product with the 27 kernel offsets SPLIT OVER THE NW WAVES of a workgroup (one 32-row x 32-channel tile per
@@ -768,30 +596,19 @@ __global__ __launch_bounds__(64 * NW) void conv16_ks_kernel(const unsigned short
     constexpr int MAXO = (27 + NW - 1) / NW;
     __shared__ __attribute__((aligned(16))) float red[NW][16][64];
     const int ct = blockIdx.y;
-    const int lane = threadIdx.x & 63, i = lane & 31, hi = lane >> 5;
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int n = *n_out;
-    const int row0 = blockIdx.x * 32;
-    if (row0 >= n) return;  // workgroup-uniform
-    const int row = row0 + i;
-    const bool valid = row < n;
-    const int lin = valid ? out_lin[row] : 0;
-    const int x = lin % go.w, y = (lin / go.w) % go.h, z = lin / (go.w * go.h);
+    ConvTile tl;
+    if (!tl.init(blockIdx.x * 32, blockIdx.x * 32, n_out, out_lin, go)) return;
+    const int lane = tl.lane, i = tl.i, hi = tl.hi, row0 = tl.row0, n = tl.n;
     int nbrs[MAXO];
 #pragma unroll
-    for (int k = 0; k < MAXO; ++k) {
+    for (int k = 0; k < MAXO; ++k) {  // wave w takes offsets w, w + NW, ...
         const int o = wv + NW * k;
-        nbrs[k] = neighbour_row(in_grid, gi, z, y, x, o < 27 ? o : 0, stride, o < 27 && valid);
+        nbrs[k] = tl.neighbour(in_grid, gi, o < 27 ? o : 0, stride, o < 27);
     }
-    f32x16 acc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+    f32x16 acc = zero_acc();
     bf16x8 ah[NC], al[NC], bh[NC], bl[NC];
-    auto load_a = [&](int nbr, int c) {
-        const size_t r = (size_t)(nbr >= 0 ? nbr : 0) * CIN + 8 * hi + 16 * c;
-        ah[c] = *reinterpret_cast<const bf16x8 *>(in_split + r);
-        al[c] = *reinterpret_cast<const bf16x8 *>(in_split + in_plane + r);
-    };
+    auto load_a = [&](int nbr, int c) { load_split_chunk<CIN>(in_split, in_plane, nbr, hi, c, ah[c], al[c]); };
     auto load_b = [&](int o, int c) {
         const bf16x8 *w = wp + ((((size_t)o * NC + c) * NTT + ct) * 2) * 64 + lane;
         bh[c] = w[0];
@@ -804,9 +621,7 @@ __global__ __launch_bounds__(64 * NW) void conv16_ks_kernel(const unsigned short
             load_b(wv, c);
         }
     }
-    bf16x8 zero;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) zero[e] = (nb_h16)0.f;
+    const bf16x8 zero = zero_fragment();
 #pragma unroll
     for (int k = 0; k < MAXO; ++k) {
         const int o = wv + NW * k;
@@ -852,19 +667,12 @@ __global__ __launch_bounds__(64 * NW) void conv16_ks_kernel(const unsigned short
     }
     s += __shfl_xor(s, 32);
     ss += __shfl_xor(ss, 32);
-    // the waves' sums meet in LDS: one atomic per channel and workgroup (store_tile_and_sums)
-    __shared__ double sred[NW][2][32];
+    __shared__ double sred[NW * 64];  // [wave][sum, sum of squares][channel]
     if (hi == 0) {
-        sred[wv][0][i] = s;
-        sred[wv][1][i] = ss;
+        sred[(wv * 2) * 32 + i] = s;
+        sred[(wv * 2 + 1) * 32 + i] = ss;
     }
-    __syncthreads();
-    if (threadIdx.x < 64) {
-        double v = 0.0;
-#pragma unroll
-        for (int w = 0; w < NW; ++w) v += sred[w][hi][i];
-        atomicAdd(&stats[hi * COUT + co], v);
-    }
+    add_channel_sums<COUT, 1, NW>(sred, ct, stats);
 }
 
 // ------------------------------------------------------------------ BatchNorm1d + ReLU (+ .dense())
@@ -951,81 +759,123 @@ inline long long bn_blocks(long long total) {
     return b < 1 ? 1 : (b > 2048 ? 2048 : b);
 }
 
-template <int CIN, int COUT>
-void launch_conv(int n_out_max, hipStream_t st, const float *in_rows, const int *in_grid, Dims gi, const int *out_lin,
-                 const int *n_out, Dims go, int stride, const float *weight, float *out_rows, double *stats) {
-    hipLaunchKernelGGL((conv_kernel<CIN, COUT>), dim3(nb_ceil_div(n_out_max, 128), (COUT + 31) / 32), dim3(256), 0, st, in_rows, in_grid,
-                       gi, out_lin, n_out, go, stride, weight, out_rows, stats);
-}
+// ------------------------------------------------------------------ which 16-bit forward kernel a layer runs
+enum class Conv16Variant {
+    KS,              // conv16_ks_kernel: one 32-row x 32-channel tile per workgroup, the offsets split over 8 waves
+    LDS_ALL_TILES,   // conv16_lds_kernel, every channel tile in each wave
+    LDS_TWO_TILES,   // conv16_lds_kernel, two channel tiles per wave (128-row x 64-channel workgroups)
+    WAVE_ALL_TILES,  // conv16_kernel, every channel tile in each wave
+    WAVE_ONE_TILE,   // conv16_kernel, one channel tile per wave
+};
 
-}  // namespace
-
-template <bool BF>
-static int conv16_dispatch(const uint16_t *in_split, int32_t in_rows_cap, const int32_t *in_grid, Dims gi, const int32_t *out_lin,
-                           const int32_t *n_out, int32_t n_out_max, Dims go, int32_t stride, const uint16_t *wpacked, int32_t cin,
-                           int32_t cout, float *out_rows, double *stats, hipStream_t st) {
-    const long long plane = (long long)in_rows_cap * cin;
-    const int row_groups = (int)nb_ceil_div(n_out_max, 128);
+Conv16Variant conv16_variant(int cin, int cout, int n_out_max) {
+    const int row_groups = nb_ceil_div(n_out_max, 128), ntt = cout / 32;
     // small levels (the deepest one of the SMPL grid: ~1.6 k rows): the launch is a handful of workgroups whichever way it is
     // tiled, so the chain of dependent L2 round trips per workgroup is what counts — offsets split over 8 waves (24 us instead
     // of 67-98 us per 128-channel layer); larger levels are L2-bandwidth-bound under that tiling (weights per 32 rows)
-    if (n_out_max <= 4096) {
-#define NB_CONV16_KS_CASE(CI, CO)                                                                                           \
-    if (cin == CI && cout == CO) {                                                                                          \
-        hipLaunchKernelGGL((conv16_ks_kernel<CI, CO, 8, BF>), dim3((unsigned)nb_ceil_div(n_out_max, 32), CO / 32), dim3(512), 0, st, \
-                           in_split, plane, in_grid, gi, out_lin, n_out, go, stride, reinterpret_cast<const bf16x8 *>(wpacked), \
-                           out_rows, stats);                                                                                \
-        NB_CHECK_LAUNCH("nb_enc_conv16");                                                                                   \
-        return NB_OK;                                                                                                       \
-    }
-        NB_CONV16_KS_CASE(32, 32)
-        NB_CONV16_KS_CASE(32, 64)
-        NB_CONV16_KS_CASE(64, 32)
-        NB_CONV16_KS_CASE(64, 64)
-        NB_CONV16_KS_CASE(64, 128)
-        NB_CONV16_KS_CASE(128, 64)
-        NB_CONV16_KS_CASE(128, 128)
-#undef NB_CONV16_KS_CASE
-    }
+    if (n_out_max <= 4096) return Conv16Variant::KS;
     // 64- and 128-channel layers: weight slab shared through LDS (measured slower for the 32-channel ones: 35 vs 29 us); all channel
-    // tiles per wave when the rows alone give >= 512 workgroups, else two per wave (128-row x 64-channel workgroups)
-#define NB_CONV16_LDS_CASE(CI, CO)                                                                                          \
-    if (cin == CI && cout == CO) {                                                                                           \
-        constexpr int NTT = CO / 32;                                                                                        \
-        if (row_groups >= 512 || NTT <= 2)                                                                                  \
-            hipLaunchKernelGGL((conv16_lds_kernel<CI, CO, NTT, BF>), dim3(row_groups, 1), dim3(256), 0, st, in_split, plane, in_grid, \
-                               gi, out_lin, n_out, go, stride, reinterpret_cast<const bf16x8 *>(wpacked), out_rows, stats); \
-        else                                                                                                                \
-            hipLaunchKernelGGL((conv16_lds_kernel<CI, CO, 2, BF>), dim3(row_groups, NTT / 2), dim3(256), 0, st, in_split, plane, \
-                               in_grid, gi, out_lin, n_out, go, stride, reinterpret_cast<const bf16x8 *>(wpacked), out_rows,     \
-                               stats);                                                                                      \
-        NB_CHECK_LAUNCH("nb_enc_conv16");                                                                                   \
-        return NB_OK;                                                                                                       \
+    // tiles per wave when the rows alone give >= 512 workgroups, else two per wave
+    if (cin >= 64) return row_groups >= 512 || ntt <= 2 ? Conv16Variant::LDS_ALL_TILES : Conv16Variant::LDS_TWO_TILES;
+    return row_groups * 4 >= 2048 || ntt == 1 ? Conv16Variant::WAVE_ALL_TILES : Conv16Variant::WAVE_ONE_TILE;
+}
+
+struct Conv16Args {
+    const unsigned short *in_split;
+    long long in_plane;
+    const int *in_grid;
+    Dims gi;
+    const int *out_lin, *n_out;
+    int n_out_max;
+    Dims go;
+    int stride;
+    const bf16x8 *wp;
+    int cin, cout;
+    float *out_rows;
+    double *stats;
+    hipStream_t st;
+};
+
+template <auto Kernel>
+void launch_conv16(dim3 grid, unsigned block, const Conv16Args &a) {
+    hipLaunchKernelGGL(Kernel, grid, dim3(block), 0, a.st, a.in_split, a.in_plane, a.in_grid, a.gi, a.out_lin, a.n_out, a.go, a.stride, a.wp,
+                       a.out_rows, a.stats);
+}
+
+// launches the layer if its channel pair is CI -> CO (false: it is not).  The 16-bit kernels take 32 channels and more on either side.
+template <int CI, int CO, bool BF>
+bool launch_conv16_if(const Conv16Args &a) {
+    if constexpr (CI < 32 || CO < 32) {
+        return false;
+    } else {
+        if (a.cin != CI || a.cout != CO) return false;
+        constexpr int NTT = CO / 32;
+        const unsigned row_groups = (unsigned)nb_ceil_div(a.n_out_max, 128);
+        switch (conv16_variant(CI, CO, a.n_out_max)) {
+        case Conv16Variant::KS:
+            launch_conv16<conv16_ks_kernel<CI, CO, 8, BF>>(dim3((unsigned)nb_ceil_div(a.n_out_max, 32), NTT), 512, a);
+            break;
+        case Conv16Variant::LDS_ALL_TILES:
+            if constexpr (CI >= 64) launch_conv16<conv16_lds_kernel<CI, CO, NTT, BF>>(dim3(row_groups, 1), 256, a);
+            break;
+        case Conv16Variant::LDS_TWO_TILES:
+            if constexpr (CI >= 64 && NTT > 2) launch_conv16<conv16_lds_kernel<CI, CO, 2, BF>>(dim3(row_groups, NTT / 2), 256, a);
+            break;
+        case Conv16Variant::WAVE_ALL_TILES:
+            if constexpr (CI < 64) launch_conv16<conv16_kernel<CI, CO, NTT, BF>>(dim3(row_groups, 1), 256, a);
+            break;
+        case Conv16Variant::WAVE_ONE_TILE:
+            if constexpr (CI < 64 && NTT > 1) launch_conv16<conv16_kernel<CI, CO, 1, BF>>(dim3(row_groups, NTT), 256, a);
+            break;
+        }
+        return true;
     }
-    NB_CONV16_LDS_CASE(64, 32)
-    NB_CONV16_LDS_CASE(64, 64)
-    NB_CONV16_LDS_CASE(64, 128)
-    NB_CONV16_LDS_CASE(128, 64)
-    NB_CONV16_LDS_CASE(128, 128)
-#undef NB_CONV16_LDS_CASE
-#define NB_CONV16_CASE(CI, CO)                                                                                              \
-    if (cin == CI && cout == CO) {                                                                                          \
-        constexpr int NTT = CO / 32;                                                                                        \
-        if (row_groups * 4 >= 2048 || NTT == 1)                                                                             \
-            hipLaunchKernelGGL((conv16_kernel<CI, CO, NTT, BF>), dim3(row_groups, 1), dim3(256), 0, st, in_split, plane, in_grid, gi, \
-                               out_lin, n_out, go, stride, reinterpret_cast<const bf16x8 *>(wpacked), out_rows, stats);     \
-        else                                                                                                                \
-            hipLaunchKernelGGL((conv16_kernel<CI, CO, 1, BF>), dim3(row_groups, NTT), dim3(256), 0, st, in_split, plane, in_grid, gi, \
-                               out_lin, n_out, go, stride, reinterpret_cast<const bf16x8 *>(wpacked), out_rows, stats);     \
-        NB_CHECK_LAUNCH("nb_enc_conv16");                                                                                   \
-        return NB_OK;                                                                                                       \
+}
+
+// a layer's pair, or the pair of its backward-input convolution (Cout -> Cin)
+template <bool BF>
+int conv16_dispatch(const Conv16Args &a) {
+#define X(CI, CO)                                                               \
+    if (launch_conv16_if<CI, CO, BF>(a) || launch_conv16_if<CO, CI, BF>(a)) { \
+        NB_CHECK_LAUNCH("nb_enc_conv16");                                       \
+        return NB_OK;                                                           \
     }
-    NB_CONV16_CASE(32, 32)
-    NB_CONV16_CASE(32, 64)
-#undef NB_CONV16_CASE
-    nb_set_error("nb_enc_conv16: unsupported channel pair %d -> %d", cin, cout);
+    NB_FOR_CONV_SHAPES(X)
+#undef X
+    nb_set_error("nb_enc_conv16: unsupported channel pair %d -> %d", a.cin, a.cout);
     return NB_EINVAL;
 }
+
+// nb_enc_bn_relu and nb_enc_bn_relu_split: `what` names the entry point in the messages; rows_split NULL: in place on rows
+int bn_relu_launch(const char *what, float *rows, const int32_t *n_rows, int32_t n_rows_max, int32_t c, const double *stats,
+                   const float *gamma, const float *beta, float *running_mean, float *running_var, int training, float eps,
+                   float momentum, float *batch_stats, const int32_t *rows_lin, float *dense, uint16_t *rows_split, float *rows_out,
+                   void *stream) {
+    NB_REQUIRE(training ? stats != nullptr : (running_mean && running_var), "%s: statistics missing", what);
+    NB_REQUIRE(!(training && momentum >= 0.f) || (running_mean && running_var && batch_stats),
+               "%s: running statistics / batch_stats required to update them", what);
+    NB_REQUIRE(!dense || rows_lin, "%s: rows_lin required with dense", what);
+    NB_REQUIRE(c > 0 && n_rows_max >= (rows_split ? 1 : 0), "%s: bad sizes", what);
+    NB_REQUIRE(c % 4 == 0 && c <= BN_MAX_C, "%s: %d channels (a multiple of 4, at most %d)", what, c, BN_MAX_C);
+    const long long total = (long long)n_rows_max * c;
+    hipLaunchKernelGGL(bn_relu_kernel, dim3((unsigned)bn_blocks(total)), dim3(256), 0, (hipStream_t)stream, rows, n_rows, c, stats, gamma,
+                       beta, running_mean, running_var, training, eps, momentum, batch_stats, rows_lin, dense, rows_out,
+                       reinterpret_cast<_Float16 *>(rows_split), rows_split ? total : 0LL);
+    NB_CHECK_LAUNCH(what);
+    return NB_OK;
+}
+
+// the checks of one pack job (`job` < 0: the single entry point, which does not number its messages)
+int pack16_check(const char *what, int job, const float *weight, int32_t cin, int32_t cout, const uint16_t *packed, int32_t mode) {
+    char at[24] = "";
+    if (job >= 0) snprintf(at, sizeof at, " job %d:", job);
+    NB_REQUIRE(weight && packed, "%s:%s NULL pointer", what, at);
+    NB_REQUIRE(mode == 0 || mode == 1, "%s:%s mode %d", what, at, mode);
+    NB_REQUIRE(cin >= 16 && cin % 16 == 0 && cout >= 32 && cout % 32 == 0, "%s:%s channel pair %d -> %d", what, at, cin, cout);
+    return NB_OK;
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -1130,20 +980,15 @@ int nb_enc_conv(const float *in_rows, const int32_t *in_grid, const int32_t in_d
     const Dims gi = {in_dhw[0], in_dhw[1], in_dhw[2]}, go = {out_dhw[0], out_dhw[1], out_dhw[2]};
     if (!(flags & NB_CONV_STATS_ZEROED)) NB_HIP(hipMemsetAsync(stats, 0, 2 * (size_t)cout * sizeof(double), st));
     if (n_out_max <= 0) return NB_OK;
-#define NB_CONV_CASE(CI, CO)                                                                                     \
-    if (cin == CI && cout == CO) {                                                                               \
-        launch_conv<CI, CO>(n_out_max, st, in_rows, in_grid, gi, out_lin, n_out, go, stride, weight, out_rows, stats); \
-        NB_CHECK_LAUNCH("nb_enc_conv");                                                                          \
-        return NB_OK;                                                                                            \
+#define X(CI, CO)                                                                                                              \
+    if (cin == CI && cout == CO) {                                                                                             \
+        hipLaunchKernelGGL((conv_kernel<CI, CO>), dim3(nb_ceil_div(n_out_max, 128), (CO + 31) / 32), dim3(256), 0, st, in_rows, \
+                           in_grid, gi, out_lin, n_out, go, stride, weight, out_rows, stats);                                  \
+        NB_CHECK_LAUNCH("nb_enc_conv");                                                                                        \
+        return NB_OK;                                                                                                          \
     }
-    NB_CONV_CASE(16, 16)
-    NB_CONV_CASE(16, 32)
-    NB_CONV_CASE(32, 32)
-    NB_CONV_CASE(32, 64)
-    NB_CONV_CASE(64, 64)
-    NB_CONV_CASE(64, 128)
-    NB_CONV_CASE(128, 128)
-#undef NB_CONV_CASE
+    NB_FOR_CONV_SHAPES(X)
+#undef X
     nb_set_error("nb_enc_conv: unsupported channel pair %d -> %d", cin, cout);
     return NB_EINVAL;
 }
@@ -1153,18 +998,8 @@ int nb_enc_bn_relu(float *rows, const int32_t *n_rows, int32_t n_rows_max, int32
                    float eps, float momentum, float *batch_stats, const int32_t *rows_lin, float *dense, float *rows_out,
                    void *stream) {
     NB_REQUIRE(rows && n_rows && gamma && beta, "nb_enc_bn_relu: NULL pointer");
-    NB_REQUIRE(training ? stats != nullptr : (running_mean && running_var), "nb_enc_bn_relu: statistics missing");
-    NB_REQUIRE(!(training && momentum >= 0.f) || (running_mean && running_var && batch_stats),
-               "nb_enc_bn_relu: running statistics / batch_stats required to update them");
-    NB_REQUIRE(!dense || rows_lin, "nb_enc_bn_relu: rows_lin required with dense");
-    NB_REQUIRE(c > 0 && n_rows_max >= 0, "nb_enc_bn_relu: bad sizes");
-    NB_REQUIRE(c % 4 == 0 && c <= BN_MAX_C, "nb_enc_bn_relu: %d channels (a multiple of 4, at most %d)", c, BN_MAX_C);
-    const long long total = (long long)n_rows_max * c;
-    hipLaunchKernelGGL(bn_relu_kernel, dim3((unsigned)bn_blocks(total)), dim3(256), 0, (hipStream_t)stream, rows, n_rows,
-                       c, stats, gamma, beta, running_mean, running_var, training, eps, momentum, batch_stats, rows_lin, dense, rows_out,
-                       (_Float16 *)nullptr, 0LL);
-    NB_CHECK_LAUNCH("nb_enc_bn_relu");
-    return NB_OK;
+    return bn_relu_launch("nb_enc_bn_relu", rows, n_rows, n_rows_max, c, stats, gamma, beta, running_mean, running_var, training, eps,
+                          momentum, batch_stats, rows_lin, dense, nullptr, rows_out, stream);
 }
 
 int nb_enc_bn_relu_split(const float *rows, const int32_t *n_rows, int32_t n_rows_max, int32_t c, const double *stats,
@@ -1172,29 +1007,13 @@ int nb_enc_bn_relu_split(const float *rows, const int32_t *n_rows, int32_t n_row
                          float eps, float momentum, float *batch_stats, const int32_t *rows_lin, float *dense,
                          uint16_t *rows_split, float *rows_out, void *stream) {
     NB_REQUIRE(rows && n_rows && gamma && beta && rows_split, "nb_enc_bn_relu_split: NULL pointer");
-    NB_REQUIRE(training ? stats != nullptr : (running_mean && running_var), "nb_enc_bn_relu_split: statistics missing");
-    NB_REQUIRE(!(training && momentum >= 0.f) || (running_mean && running_var && batch_stats),
-               "nb_enc_bn_relu_split: running statistics / batch_stats required to update them");
-    NB_REQUIRE(!dense || rows_lin, "nb_enc_bn_relu_split: rows_lin required with dense");
-    NB_REQUIRE(c > 0 && n_rows_max > 0, "nb_enc_bn_relu_split: bad sizes");
-    NB_REQUIRE(c % 4 == 0 && c <= BN_MAX_C, "nb_enc_bn_relu_split: %d channels (a multiple of 4, at most %d)", c, BN_MAX_C);
-    const long long total = (long long)n_rows_max * c;
-    hipLaunchKernelGGL(bn_relu_kernel, dim3((unsigned)bn_blocks(total)), dim3(256), 0, (hipStream_t)stream,
-                       const_cast<float *>(rows), n_rows, c, stats, gamma, beta, running_mean, running_var, training, eps, momentum,
-                       batch_stats, rows_lin, dense, rows_out, reinterpret_cast<_Float16 *>(rows_split), total);
-    NB_CHECK_LAUNCH("nb_enc_bn_relu_split");
-    return NB_OK;
+    return bn_relu_launch("nb_enc_bn_relu_split", const_cast<float *>(rows), n_rows, n_rows_max, c, stats, gamma, beta, running_mean,
+                          running_var, training, eps, momentum, batch_stats, rows_lin, dense, rows_split, rows_out, stream);
 }
 
 int nb_enc_conv_pack16(const float *weight, int32_t cin, int32_t cout, uint16_t *packed, int32_t mode, void *stream) {
-    NB_REQUIRE(weight && packed, "nb_enc_conv_pack16: NULL pointer");
-    NB_REQUIRE(mode == 0 || mode == 1, "nb_enc_conv_pack16: mode %d", mode);
-    NB_REQUIRE(cin >= 16 && cin % 16 == 0 && cout >= 32 && cout % 32 == 0, "nb_enc_conv_pack16: channel pair %d -> %d", cin, cout);
-    const long long n = 27LL * (cin / 16) * (cout / 32) * 2 * 64;
-    hipLaunchKernelGGL(conv_pack16_kernel, dim3(nb_ceil_div(n, 256)), dim3(256), 0, (hipStream_t)stream, weight, cin, cout,
-                       reinterpret_cast<bf16x8 *>(packed), mode);
-    NB_CHECK_LAUNCH("nb_enc_conv_pack16");
-    return NB_OK;
+    if (int e = pack16_check("nb_enc_conv_pack16", -1, weight, cin, cout, packed, mode)) return e;
+    return nb_enc_conv_pack16_batch(1, &weight, &cin, &cout, &packed, &mode, stream);  // (its launch error would name the batch entry)
 }
 
 int nb_enc_conv_pack16_batch(int32_t n_jobs, const float *const weight[], const int32_t cin[], const int32_t cout[],
@@ -1205,10 +1024,7 @@ int nb_enc_conv_pack16_batch(int32_t n_jobs, const float *const weight[], const 
     PackBatch b = {};
     long long most = 0;
     for (int i = 0; i < n_jobs; ++i) {
-        NB_REQUIRE(weight[i] && packed[i], "nb_enc_conv_pack16_batch: job %d: NULL pointer", i);
-        NB_REQUIRE(mode[i] == 0 || mode[i] == 1, "nb_enc_conv_pack16_batch: job %d: mode %d", i, mode[i]);
-        NB_REQUIRE(cin[i] >= 16 && cin[i] % 16 == 0 && cout[i] >= 32 && cout[i] % 32 == 0, "nb_enc_conv_pack16_batch: job %d: channel pair %d -> %d",
-                   i, cin[i], cout[i]);
+        if (int e = pack16_check("nb_enc_conv_pack16_batch", i, weight[i], cin[i], cout[i], packed[i], mode[i])) return e;
         b.w[i] = weight[i];
         b.out[i] = reinterpret_cast<bf16x8 *>(packed[i]);
         b.cin[i] = cin[i];
@@ -1234,10 +1050,9 @@ int nb_enc_conv16(const uint16_t *in_split, int32_t in_rows_cap, const int32_t *
     const Dims gi = {in_dhw[0], in_dhw[1], in_dhw[2]}, go = {out_dhw[0], out_dhw[1], out_dhw[2]};
     if (!(flags & NB_CONV_STATS_ZEROED)) NB_HIP(hipMemsetAsync(stats, 0, 2 * (size_t)cout * sizeof(double), st));
     if (n_out_max <= 0) return NB_OK;
-    return (flags & NB_CONV_BF16) ? conv16_dispatch<true>(in_split, in_rows_cap, in_grid, gi, out_lin, n_out, n_out_max, go, stride, wpacked,
-                                                          cin, cout, out_rows, stats, st)
-                                  : conv16_dispatch<false>(in_split, in_rows_cap, in_grid, gi, out_lin, n_out, n_out_max, go, stride, wpacked,
-                                                           cin, cout, out_rows, stats, st);
+    const Conv16Args a = {in_split, (long long)in_rows_cap * cin, in_grid, gi, out_lin, n_out, n_out_max, go, stride,
+                          reinterpret_cast<const bf16x8 *>(wpacked), cin, cout, out_rows, stats, st};
+    return (flags & NB_CONV_BF16) ? conv16_dispatch<true>(a) : conv16_dispatch<false>(a);
 }
 
 int nb_enc_gather_codes(const float *codes, const int32_t *rows_vert, const int32_t *n_rows, int32_t n_rows_max,

@@ -11,20 +11,10 @@
 //   nb_enc_conv_bwd_weight  dW[o] = sum_r in[nbr(r, o)]^T (x) dx[r]   (MFMA over row chunks, fp32 atomics into dW)
 //   nb_enc_scatter_codes_bwd  d c.weight[vertex of row r] = d rows[r]  (Embedding lookup backward, :33-34)
 #include "nb_common.h"
+#include "nb_enc_tile.h"
 #include "nb_trread.h"
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-#define NB_MFMA(a, b, c) __builtin_amdgcn_mfma_f32_32x32x2f32((a), (b), (c), 0, 0, 0)
-
 namespace {
-
-struct Dims {
-    int d, h, w;
-};
-
-__host__ __device__ constexpr int tile_row(int r, int hi) { return (r & 3) + 8 * (r >> 2) + 4 * hi; }
 
 // ------------------------------------------------------------------ BatchNorm + ReLU backward
 __global__ __launch_bounds__(1024) void bn_bwd_reduce_kernel(const float *__restrict__ dy, const float *__restrict__ y,
@@ -116,61 +106,27 @@ __global__ __launch_bounds__(256, 2) void conv_bwd_in_kernel(const float *__rest
                                                           const float *__restrict__ weight, float *__restrict__ din) {
     constexpr int HALF = COUT / 2;
     const int ct = blockIdx.y;
-    const int lane = threadIdx.x & 63, i = lane & 31, hi = lane >> 5;
-    const int wave = blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int n = *n_in;
-    const int row0 = wave * 32;
-    if (row0 >= n) return;
-    const int row = row0 + i;
-    const bool valid = row < n;
-    const int lin = valid ? in_lin[row] : 0;
-    const int x = lin % gi.w, y = (lin / gi.w) % gi.h, z = lin / (gi.w * gi.h);
-    f32x16 acc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-    // output voxel u with u * stride - 1 + k == p, for every offset first (27 independent lookups), then — on the narrow layers,
-    // where a second set of row registers is cheap — the dx rows of offset o + 1 while offset o multiplies: as a chain of lookup ->
-    // row -> MFMA per offset the 16 <- 32 layer took 70 us for 6.9 k rows
+    ConvTile tl;
+    const int row0 = (blockIdx.x * 4 + (threadIdx.x >> 6)) * 32;
+    if (!tl.init(row0, row0, n_in, in_lin, gi)) return;  // (no barrier in this kernel: each wave leaves on its own)
+    const int i = tl.i, hi = tl.hi, n = tl.n;
+    f32x16 acc = zero_acc();
+    // output voxel u with u * stride - 1 + k == p — the transposed gather under the mirrored offset — for every offset first (27
+    // independent lookups), then — on the narrow layers, where a second set of row registers is cheap — the dx rows of offset o + 1
+    // while offset o multiplies: as a chain of lookup -> row -> MFMA per offset the 16 <- 32 layer took 70 us for 6.9 k rows
     int nbrs[27];
-#pragma unroll
-    for (int o = 0; o < 27; ++o) {
-        const int kd = o / 9, kh = (o / 3) % 3, kw = o % 3;
-        const int nz = z + 1 - kd, ny = y + 1 - kh, nx = x + 1 - kw;
-        int nbr = -1;
-        bool ok = valid && nz >= 0 && ny >= 0 && nx >= 0;
-        int uz = nz, uy = ny, ux = nx;
-        if (stride == 2) {
-            ok = ok && !(nz & 1) && !(ny & 1) && !(nx & 1);
-            uz = nz >> 1;
-            uy = ny >> 1;
-            ux = nx >> 1;
-        }
-        if (ok && uz < go.d && uy < go.h && ux < go.w) nbr = out_grid[((long long)uz * go.h + uy) * go.w + ux];
-        nbrs[o] = nbr;
-    }
+    tl.fill_neighbours<true>(nbrs, out_grid, go, stride);
     constexpr bool AHEAD = HALF <= 16;
     f32x4 Ar[AHEAD ? 2 : 1][HALF / 4];
-    auto load_rows = [&](int nbr, f32x4 (&dst)[HALF / 4]) {  // (row 0 for a lane without a neighbour: zeroed below)
-        const f32x4 *p = reinterpret_cast<const f32x4 *>(dx + (size_t)(nbr >= 0 ? nbr : 0) * COUT + hi * HALF);
-#pragma unroll
-        for (int q = 0; q < HALF / 4; ++q) dst[q] = p[q];
-    };
-    if (AHEAD) load_rows(nbrs[0], Ar[0]);
+    if (AHEAD) load_row_half<COUT>(dx, nbrs[0], hi, Ar[0]);
 #pragma unroll
     for (int o = 0; o < 27; ++o) {
-        if (AHEAD && o + 1 < 27) load_rows(nbrs[o + 1], Ar[(o + 1) & 1]);
+        if (AHEAD && o + 1 < 27) load_row_half<COUT>(dx, nbrs[o + 1], hi, Ar[(o + 1) & 1]);
         const int nbr = nbrs[o];
         if (!__any(nbr >= 0)) continue;
-        if (!AHEAD) load_rows(nbr, Ar[0]);
+        if (!AHEAD) load_row_half<COUT>(dx, nbr, hi, Ar[0]);
         float A[HALF];
-#pragma unroll
-        for (int q = 0; q < HALF / 4; ++q) {
-            const f32x4 v = Ar[AHEAD ? (o & 1) : 0][q];
-            A[4 * q] = nbr >= 0 ? v.x : 0.f;
-            A[4 * q + 1] = nbr >= 0 ? v.y : 0.f;
-            A[4 * q + 2] = nbr >= 0 ? v.z : 0.f;
-            A[4 * q + 3] = nbr >= 0 ? v.w : 0.f;
-        }
+        mask_row_half<COUT>(Ar[AHEAD ? (o & 1) : 0], nbr >= 0, A);
         // B[k = co][j = ci] = W[o][ci][co]  (transposed read of the spconv-layout slab)
         const int ci = ct * 32 + i;
         const bool ciok = (CIN % 32 == 0) || ci < CIN;
@@ -201,14 +157,9 @@ __global__ void conv_rulebook_kernel(const int *__restrict__ in_grid, Dims gi, c
     const int n = *n_out;
     if (idx >= (long long)n * 27) return;
     const int row = (int)(idx / 27), o = (int)(idx % 27);
-    const int kd = o / 9, kh = (o / 3) % 3, kw = o % 3;
     const int lin = out_lin[row];
     const int x = lin % go.w, y = (lin / go.w) % go.h, z = lin / (go.w * go.h);
-    const int iz = z * stride - 1 + kd, iy = y * stride - 1 + kh, ix = x * stride - 1 + kw;
-    int v = -1;
-    if ((unsigned)iz < (unsigned)gi.d && (unsigned)iy < (unsigned)gi.h && (unsigned)ix < (unsigned)gi.w)
-        v = in_grid[((long long)iz * gi.h + iy) * gi.w + ix];
-    nbr[idx] = v;
+    nbr[idx] = neighbour_row(in_grid, gi, z, y, x, o, stride, true);
 }
 
 // one wave = (offset o, ci tile, co tile, chunk of ROWS_PER_WAVE output rows); D[ci][co] += sum_rows in^T dx
@@ -228,9 +179,7 @@ __global__ __launch_bounds__(256, 2) void conv_bwd_w_kernel(const float *__restr
     if (row0 >= n) return;
     const int ci = ti * 32 + i, co = to * 32 + i;
     const bool ciok = (CIN % 32 == 0) || ci < CIN, cook = (COUT % 32 == 0) || co < COUT;
-    f32x16 acc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+    f32x16 acc = zero_acc();
     bool any = false;
     for (int m0 = 0; m0 < ROWS_PER_WAVE / 2; m0 += 8) {  // 8 K=2 chunks per round: all loads issued before the MFMAs
         float a[8], b[8];
@@ -359,9 +308,7 @@ __global__ __launch_bounds__(256, 2) void conv_bwd_w16_kernel(const float *__res
 #pragma unroll
     for (int a = 0; a < TCI; ++a)
 #pragma unroll
-        for (int b = 0; b < TCO; ++b)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
+        for (int b = 0; b < TCO; ++b) acc[a][b] = zero_acc();
     // fragment addressing: lane l of 16-lane group g addresses segment (row 8 (g >> 1) + (l15 >> 2), channels 16 (g & 1) + 4 (l15 & 3))
     const int l15 = lane & 15, g = lane >> 4;
     const unsigned lds0 = (unsigned)(size_t)lds;
@@ -428,6 +375,21 @@ __global__ __launch_bounds__(256, 2) void conv_bwd_w16_kernel(const float *__res
         }
 }
 
+// bf16 pairs of dx given: the matrix-pipe kernel (the 16-channel layers stay exact fp32)
+template <int CI, int CO>
+void launch_conv_bwd_w(int n_out_max, hipStream_t st, const float *in_rows, const int *rulebook, const int *n_out, const float *dx,
+                       const uint16_t *dx_split, float *dweight) {
+    if constexpr (CI >= 32) {
+        if (dx_split) {
+            hipLaunchKernelGGL((conv_bwd_w16_kernel<CI, CO>), dim3(27, (unsigned)nb_ceil_div(n_out_max, BW_ROWS)), dim3(256), 0, st, in_rows,
+                               rulebook, n_out, dx_split, (long long)n_out_max * CO, dweight);
+            return;
+        }
+    }
+    hipLaunchKernelGGL((conv_bwd_w_kernel<CI, CO>), dim3(nb_ceil_div(n_out_max, 4 * ROWS_PER_WAVE), 27, ((CI + 31) / 32) * ((CO + 31) / 32)),
+                       dim3(256), 0, st, in_rows, rulebook, n_out, dx, dweight);
+}
+
 }  // namespace
 
 extern "C" {
@@ -451,8 +413,6 @@ int nb_enc_bn_relu_bwd(const float *dy, const float *y, const float *x, const in
     NB_CHECK_LAUNCH("nb_enc_bn_relu_bwd");
     return NB_OK;
 }
-
-#define NB_FOR_CONV_SHAPES(X) X(16, 16) X(16, 32) X(32, 32) X(32, 64) X(64, 64) X(64, 128) X(128, 128)
 
 int nb_enc_conv_bwd_input(const float *dx, const int32_t *out_grid, const int32_t out_dhw[3], const int32_t *in_lin,
                           const int32_t *n_in, int32_t n_in_max, const int32_t in_dhw[3], int32_t stride,
@@ -490,25 +450,11 @@ int nb_enc_conv_bwd_weight(const float *in_rows, const int32_t *in_grid, const i
     if (!(flags & NB_BWD_RULEBOOK_READY))
         hipLaunchKernelGGL(conv_rulebook_kernel, dim3(nb_ceil_div((long long)n_out_max * 27, 256)), dim3(256), 0, st, in_grid, gi,
                            out_lin, n_out, go, stride, rulebook);
-    if (dx_split && cin >= 32) {  // bf16 pairs of dx given: the matrix-pipe kernel (the 16-channel layers stay exact fp32)
-        const long long plane = (long long)n_out_max * cout;
-#define X16(CI, CO)                                                                                                   \
-    if (cin == CI && cout == CO) {                                                                                    \
-        hipLaunchKernelGGL((conv_bwd_w16_kernel<CI, CO>), dim3(27, (unsigned)nb_ceil_div(n_out_max, BW_ROWS)), dim3(256), 0, st, \
-                           in_rows, rulebook, n_out, dx_split, plane, dweight);                                       \
-        NB_CHECK_LAUNCH("nb_enc_conv_bwd_weight");                                                                    \
-        return NB_OK;                                                                                                 \
-    }
-        X16(32, 32) X16(32, 64) X16(64, 64) X16(64, 128) X16(128, 128)
-#undef X16
-    }
-#define X(CI, CO)                                                                                                     \
-    if (cin == CI && cout == CO) {                                                                                    \
-        hipLaunchKernelGGL((conv_bwd_w_kernel<CI, CO>),                                                               \
-                           dim3(nb_ceil_div(n_out_max, 4 * ROWS_PER_WAVE), 27, ((CI + 31) / 32) * ((CO + 31) / 32)),  \
-                           dim3(256), 0, st, in_rows, rulebook, n_out, dx, dweight);                                   \
-        NB_CHECK_LAUNCH("nb_enc_conv_bwd_weight");                                                                    \
-        return NB_OK;                                                                                                 \
+#define X(CI, CO)                                                                                                        \
+    if (cin == CI && cout == CO) {                                                                                       \
+        launch_conv_bwd_w<CI, CO>(n_out_max, st, in_rows, rulebook, n_out, dx, dx_split, dweight);                       \
+        NB_CHECK_LAUNCH("nb_enc_conv_bwd_weight");                                                                       \
+        return NB_OK;                                                                                                    \
     }
     NB_FOR_CONV_SHAPES(X)
 #undef X

@@ -418,12 +418,9 @@ def enc_downsample_index_all(in_lin, n_in, n_in_max, in_dhw, bufs, grids, scratc
     return out
 
 
-def enc_conv(in_rows, in_grid, in_dhw, out_lin, n_out, n_out_max, out_dhw, stride, weight, stats=None):
-    """nb_enc_conv -> (out_rows [n_out_max, Cout], stats [2*Cout] fp64).  `stats`: a ZEROED fp64 [2*Cout] buffer of the
-    caller's (the encoder clears the statistics of all its layers with one fill) — else the call allocates and clears one."""
-    _req(weight, torch.float32, (3, 3, 3, None, None), "conv weight")
-    cin, cout = int(weight.shape[3]), int(weight.shape[4])
-    _req(in_rows, torch.float32, (None, cin), "in_rows")
+def _enc_conv(entry, in_rows, cin, cout, in_grid, in_dhw, out_lin, n_out, n_out_max, out_dhw, stride, weight, stats, flags, pre=()):
+    """enc_conv / enc_conv16: the index-set and statistics checks, the outputs and the call (`pre`: what the entry point takes
+    between the rows and the grid).  flags: bit 0 (NB_CONV_STATS_ZEROED) is set here."""
     _req(in_grid, torch.int32, tuple(int(s) for s in in_dhw), "in_grid")
     _req(out_lin, torch.int32, (None,), "out_lin")
     _req(n_out, torch.int32, (1,), "n_out")
@@ -431,21 +428,29 @@ def enc_conv(in_rows, in_grid, in_dhw, out_lin, n_out, n_out_max, out_dhw, strid
         raise ValueError("out_lin shorter than n_out_max")
     dev = in_rows.device
     out_rows = torch.empty((max(int(n_out_max), 1), cout), dtype=torch.float32, device=dev)
-    flags = 0 if stats is None else 1  # NB_CONV_STATS_ZEROED
     if stats is None:
         stats = torch.empty(2 * cout, dtype=torch.float64, device=dev)
     else:
         _req(stats, torch.float64, (2 * cout,), "stats")
-    check(_lib.lib().nb_enc_conv(ptr(in_rows), ptr(in_grid), _i3(in_dhw), ptr(out_lin), ptr(n_out), int(n_out_max),
-                                 _i3(out_dhw), int(stride), ptr(weight), cin, cout, ptr(out_rows), ptr(stats), flags,
-                                 _stream()), "nb_enc_conv")
+        flags |= 1
+    check(getattr(_lib.lib(), entry)(ptr(in_rows), *pre, ptr(in_grid), _i3(in_dhw), ptr(out_lin), ptr(n_out), int(n_out_max),
+                                     _i3(out_dhw), int(stride), ptr(weight), cin, cout, ptr(out_rows), ptr(stats), flags,
+                                     _stream()), entry)
     return out_rows, stats
 
 
-def enc_bn_relu(rows, n_rows, n_rows_max, stats, gamma, beta, running_mean, running_var, training, eps,
-                rows_lin=None, dense=None, momentum=-1.0, rows_out=None):
-    """nb_enc_bn_relu (in place on rows) -> batch_stats [2C+1] = mean | biased var | n_rows.
-    momentum >= 0 (training only): running_mean / running_var are updated in place by the kernel."""
+def enc_conv(in_rows, in_grid, in_dhw, out_lin, n_out, n_out_max, out_dhw, stride, weight, stats=None):
+    """nb_enc_conv -> (out_rows [n_out_max, Cout], stats [2*Cout] fp64).  `stats`: a ZEROED fp64 [2*Cout] buffer of the
+    caller's (the encoder clears the statistics of all its layers with one fill) — else the call allocates and clears one."""
+    _req(weight, torch.float32, (3, 3, 3, None, None), "conv weight")
+    cin, cout = int(weight.shape[3]), int(weight.shape[4])
+    _req(in_rows, torch.float32, (None, cin), "in_rows")
+    return _enc_conv("nb_enc_conv", in_rows, cin, cout, in_grid, in_dhw, out_lin, n_out, n_out_max, out_dhw, stride, weight, stats, 0)
+
+
+def _enc_bn_relu(entry, rows, n_rows, n_rows_max, stats, gamma, beta, running_mean, running_var, training, eps, rows_lin, dense,
+                 momentum, rows_out, split=None):
+    """enc_bn_relu / enc_bn_relu_split: the checks, batch_stats and the call (split: the second one's extra output)."""
     c = int(rows.shape[1])
     _req(rows, torch.float32, (None, c), "rows")
     for t, nm in ((gamma, "gamma"), (beta, "beta"), (running_mean, "running_mean"), (running_var, "running_var")):
@@ -458,11 +463,19 @@ def enc_bn_relu(rows, n_rows, n_rows_max, stats, gamma, beta, running_mean, runn
     if rows_out is not None:
         _req(rows_out, torch.float32, tuple(rows.shape), "rows_out")
     batch_stats = torch.empty(2 * c + 1, dtype=torch.float32, device=rows.device)
-    check(_lib.lib().nb_enc_bn_relu(ptr(rows), ptr(n_rows), int(n_rows_max), c, ptr(stats), ptr(gamma), ptr(beta),
-                                    ptr(running_mean), ptr(running_var), 1 if training else 0, float(eps),
-                                    float(momentum), ptr(batch_stats), ptr(rows_lin), ptr(dense), ptr(rows_out),
-                                    _stream()), "nb_enc_bn_relu")
+    check(getattr(_lib.lib(), entry)(ptr(rows), ptr(n_rows), int(n_rows_max), c, ptr(stats), ptr(gamma), ptr(beta),
+                                     ptr(running_mean), ptr(running_var), 1 if training else 0, float(eps), float(momentum),
+                                     ptr(batch_stats), ptr(rows_lin), ptr(dense), *(() if split is None else (ptr(split),)),
+                                     ptr(rows_out), _stream()), entry)
     return batch_stats
+
+
+def enc_bn_relu(rows, n_rows, n_rows_max, stats, gamma, beta, running_mean, running_var, training, eps,
+                rows_lin=None, dense=None, momentum=-1.0, rows_out=None):
+    """nb_enc_bn_relu (in place on rows) -> batch_stats [2C+1] = mean | biased var | n_rows.
+    momentum >= 0 (training only): running_mean / running_var are updated in place by the kernel."""
+    return _enc_bn_relu("nb_enc_bn_relu", rows, n_rows, n_rows_max, stats, gamma, beta, running_mean, running_var, training, eps,
+                        rows_lin, dense, momentum, rows_out)
 
 
 def enc_conv_pack16(weight, backward_input=False):
@@ -472,10 +485,8 @@ def enc_conv_pack16(weight, backward_input=False):
     _req(weight, torch.float32, (3, 3, 3, None, None), "conv weight")
     cin, cout = int(weight.shape[3]), int(weight.shape[4])
     packed = torch.empty(27 * cin * cout * 2, dtype=torch.int16, device=weight.device)
-    if backward_input:
-        check(_lib.lib().nb_enc_conv_pack16(ptr(weight), cout, cin, ptr(packed), 1, _stream()), "nb_enc_conv_pack16")
-    else:
-        check(_lib.lib().nb_enc_conv_pack16(ptr(weight), cin, cout, ptr(packed), 0, _stream()), "nb_enc_conv_pack16")
+    ci, co, mode = (cout, cin, 1) if backward_input else (cin, cout, 0)
+    check(_lib.lib().nb_enc_conv_pack16(ptr(weight), ci, co, ptr(packed), mode, _stream()), "nb_enc_conv_pack16")
     return packed
 
 
@@ -505,48 +516,20 @@ def enc_conv16(in_split, in_grid, in_dhw, out_lin, n_out, n_out_max, out_dhw, st
     in enc_conv.  bf16: the planes and the packed weight are bf16 pairs (the backward-input convolution)."""
     _req(in_split, torch.int16, (2, None, cin), "in_split")
     _req(wpacked, torch.int16, (27 * cin * cout * 2,), "wpacked")
-    _req(in_grid, torch.int32, tuple(int(s) for s in in_dhw), "in_grid")
-    _req(out_lin, torch.int32, (None,), "out_lin")
-    _req(n_out, torch.int32, (1,), "n_out")
-    if out_lin.shape[0] < n_out_max:
-        raise ValueError("out_lin shorter than n_out_max")
-    dev = in_split.device
-    out_rows = torch.empty((max(int(n_out_max), 1), cout), dtype=torch.float32, device=dev)
-    flags = (0 if stats is None else 1) | (2 if bf16 else 0)  # NB_CONV_STATS_ZEROED | NB_CONV_BF16
-    if stats is None:
-        stats = torch.empty(2 * cout, dtype=torch.float64, device=dev)
-    else:
-        _req(stats, torch.float64, (2 * cout,), "stats")
-    check(_lib.lib().nb_enc_conv16(ptr(in_split), int(in_split.shape[1]), ptr(in_grid), _i3(in_dhw), ptr(out_lin), ptr(n_out),
-                                   int(n_out_max), _i3(out_dhw), int(stride), ptr(wpacked), cin, cout, ptr(out_rows),
-                                   ptr(stats), flags, _stream()), "nb_enc_conv16")
-    return out_rows, stats
+    return _enc_conv("nb_enc_conv16", in_split, cin, cout, in_grid, in_dhw, out_lin, n_out, n_out_max, out_dhw, stride, wpacked, stats,
+                     2 if bf16 else 0, pre=(int(in_split.shape[1]),))  # NB_CONV_BF16
 
 
 def enc_bn_relu_split(rows, n_rows, n_rows_max, stats, gamma, beta, running_mean, running_var, training, eps,
                       rows_lin=None, dense=None, momentum=-1.0, rows_out=None):
     """nb_enc_bn_relu_split -> (rows_split int16 [2, n_rows_max, C], batch_stats); rows_out (fp32, same shape as rows):
     receives the activated rows in fp32 as well (training forward)."""
-    c = int(rows.shape[1])
-    _req(rows, torch.float32, (None, c), "rows")
-    if rows_out is not None:
-        _req(rows_out, torch.float32, tuple(rows.shape), "rows_out")
-    for t, nm in ((gamma, "gamma"), (beta, "beta"), (running_mean, "running_mean"), (running_var, "running_var")):
-        _req(t, torch.float32, (c,), nm)
-    if stats is not None:
-        _req(stats, torch.float64, (2 * c,), "stats")
-    if dense is not None:
-        _req(dense, torch.float32, (None, None, None, c), "dense")
-        _req(rows_lin, torch.int32, (None,), "rows_lin")
     n_rows_max = max(int(n_rows_max), 1)
     if rows.shape[0] < n_rows_max:
         raise ValueError("rows shorter than n_rows_max")
-    split = torch.empty((2, n_rows_max, c), dtype=torch.int16, device=rows.device)
-    batch_stats = torch.empty(2 * c + 1, dtype=torch.float32, device=rows.device)
-    check(_lib.lib().nb_enc_bn_relu_split(ptr(rows), ptr(n_rows), n_rows_max, c, ptr(stats), ptr(gamma), ptr(beta),
-                                          ptr(running_mean), ptr(running_var), 1 if training else 0, float(eps),
-                                          float(momentum), ptr(batch_stats), ptr(rows_lin), ptr(dense), ptr(split),
-                                          ptr(rows_out), _stream()), "nb_enc_bn_relu_split")
+    split = torch.empty((2, n_rows_max, int(rows.shape[1])), dtype=torch.int16, device=rows.device)
+    batch_stats = _enc_bn_relu("nb_enc_bn_relu_split", rows, n_rows, n_rows_max, stats, gamma, beta, running_mean, running_var,
+                               training, eps, rows_lin, dense, momentum, rows_out, split)
     return split, batch_stats
 
 

@@ -279,6 +279,50 @@ def test_encoder_backward_matches_autograd():
     print("encoder backward: worst max|diff|/max|ref| = %.2e over 52 tensors" % worst)
 
 
+def test_neighbour_table_and_backward_input_follow_the_index_rule():
+    """The one device function that states the spconv index rule, from both of its call directions, on a (5, 6, 7) grid with 40
+    active voxels (all eight corners among them), stride 1 and 2: the neighbour table that enc_conv_bwd_weight leaves in
+    `rulebook` (forward gather) against a loop over (row, offset) of in = stride * out - 1 + k, and enc_conv_bwd_input
+    (transposed gather under the mirrored offset) against a float64 scatter over that same table."""
+    from neuralbody_amd import ops
+
+    dhw, cin, cout = (5, 6, 7), 16, 32
+    rs = np.random.RandomState(3)
+    corners = [(z, y, x) for z in (0, dhw[0] - 1) for y in (0, dhw[1] - 1) for x in (0, dhw[2] - 1)]
+    rest = [c for c in np.ndindex(*dhw) if c not in corners]
+    coord = np.array(corners + [rest[i] for i in rs.choice(len(rest), 32, replace=False)], np.int32)
+    n_in = len(coord)
+    in_grid, _, in_lin, n_rows = ops.enc_voxelize(torch.from_numpy(coord).to(DEV), dhw)
+    assert int(n_rows) == n_in
+    weight = torch.from_numpy(rs.standard_normal((3, 3, 3, cin, cout)).astype(np.float32)).to(DEV)
+    in_rows = torch.from_numpy(rs.standard_normal((n_in, cin)).astype(np.float32)).to(DEV)
+    grid_np = in_grid.cpu().numpy()
+    for stride in (1, 2):
+        if stride == 1:
+            out_grid, out_lin, n_out, n_out_max, out_dhw = in_grid, in_lin, n_rows, n_in, list(dhw)
+        else:
+            out_grid, out_lin, n_out, n_out_max, out_dhw = ops.enc_downsample_index(in_lin, n_rows, n_in, dhw)
+        no = int(n_out)
+        dx = torch.from_numpy(rs.standard_normal((n_out_max, cout)).astype(np.float32)).to(DEV)
+        rulebook = []
+        ops.enc_conv_bwd_weight(in_rows, in_grid, dhw, out_lin, n_out, n_out_max, out_dhw, stride, dx, cin, cout, rulebook=rulebook)
+        got = rulebook[0].cpu().numpy().reshape(-1, 27)[:no]
+        want = np.full((no, 27), -1, np.int32)
+        for r, (z, y, x) in enumerate(zip(*np.unravel_index(out_lin[:no].cpu().numpy(), out_dhw))):
+            for o, (kd, kh, kw) in enumerate(np.ndindex(3, 3, 3)):
+                i = (stride * z - 1 + kd, stride * y - 1 + kh, stride * x - 1 + kw)
+                if all(0 <= v < s for v, s in zip(i, dhw)):
+                    want[r, o] = grid_np[i]
+        assert (want >= 0).sum() > no, "stride %d: the table has neighbours beyond the centres" % stride
+        np.testing.assert_array_equal(got, want, err_msg="neighbour table, stride %d" % stride)
+        din = ops.enc_conv_bwd_input(dx, out_grid, out_dhw, in_lin, n_rows, n_in, dhw, stride, weight)
+        ref = np.zeros((n_in, cin))
+        w64, dx64 = weight.cpu().numpy().astype(np.float64).reshape(27, cin, cout), dx.cpu().numpy().astype(np.float64)
+        for r, o in zip(*np.nonzero(want >= 0)):
+            ref[want[r, o]] += w64[o] @ dx64[r]
+        _rel(din.cpu().numpy(), ref, ENC_TOL, "din, stride %d" % stride)
+
+
 def test_full_training_step_gradients_match_autograd():
     """Renderer.render under autograd (encoder + decode + composite, forward and backward all HIP) against float64
     autograd through the whole oracle: the gradient of EVERY parameter (MLP, latent codes, 17 sparse conv weights,
