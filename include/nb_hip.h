@@ -452,6 +452,37 @@ int nb_raygen(int32_t H, int32_t W, const double K[9], const double R[9], const 
               uint8_t *mask_at_box, int32_t *n_rays, void *scratch, void *stream);
 
 /* ---------------------------------------------------------------------------------
+ * nb_train_rays — replaces the train branch of sample_ray_h36m / sample_ray
+ * (lib/utils/if_nerf/if_nerf_data_utils.py:153-219 / :72-137, called per item by lib/datasets/light_stage/
+ * multi_view_dataset.py:154 and monocular_dataset.py) on device: one batch of n_rays training rays drawn from a resident
+ * image and mask, with get_rays (:8-21), the 2-D bound mask (:40-51) and get_near_far (:54-69) folded in.
+ *   K, R (row-major 3x3), T (3): HOST doubles; bounds: host float[6] world AABB (can_bounds: min xyz, max xyz).
+ *   hull_xy HOST int32 [n_hull,2] (x, y), n_hull in 3..8: the convex hull of the box's eight projected, rounded corners,
+ *     counter-clockwise (train_rays.bound_hull); a pixel centre inside or on it is in the bound mask (edge functions in int64).
+ *   msk dev [H*W] uint8, img dev [H*W,3] fp32.  With m = msk * in_hull:
+ *     NB_SAMPLE_H36M   body: m == 1;  bound: in_hull && m != 100   (:160-161,181,190)
+ *     NB_SAMPLE_PLAIN  body: m != 0;  bound: in_hull               (:79,99,108)
+ *   Candidates of a class are numbered in row-major order (np.argwhere) by an exclusive scan, recomputed on every call.
+ *   u dev [n_rounds, n_rays] fp32 uniforms in [0,1).  Round r with deficit m_r (m_0 = n_rays): n_body = (int)(m_r * body_ratio)
+ *     body draws, then m_r - n_body bound draws; draw j takes candidate min((int)((double)u[r,j] * count), count - 1).
+ *     The pixel's ray, the hit test and near/far are float64 (the reference hands get_near_far the float64 rays here; the
+ *     1e-5 / 1e-10 clamps in that order); rays with near < far are appended behind the earlier rounds' in draw order and
+ *     m_{r+1} = m_r - hits; it stops at m_r = 0 or after n_rounds rounds.  A class without candidates gives no hits.
+ *   outputs dev: rgb, ray_o, ray_d [n_rays,3]; near, far [n_rays] (rounded to fp32 once, on store); pixel [n_rays,2] int32
+ *     (y, x); mask_at_box [n_rays] uint8; status [4] int32 = {n_filled, rounds_used, count_body, count_bound}.
+ *     Rows >= n_filled: mask_at_box = 0, rgb = 0, pixel = (-1,-1), the ray of pixel (0,0) with near = far = 0.
+ *   No synchronisation, no atomics, no data-dependent launch: the same inputs give the same bits.
+ *   scratch dev: nb_train_rays_scratch_size(H, W) bytes (0 for sizes the call refuses: H, W < 1 or H*W > 2^30). */
+#define NB_SAMPLE_H36M 0
+#define NB_SAMPLE_PLAIN 1
+int64_t nb_train_rays_scratch_size(int32_t H, int32_t W);
+int nb_train_rays(int32_t H, int32_t W, const double K[9], const double R[9], const double T[3], const float bounds[6],
+                  const int32_t *hull_xy, int32_t n_hull, const uint8_t *msk, const float *img, int32_t mode,
+                  double body_ratio, const float *u, int32_t n_rounds, int32_t n_rays, float *rgb, float *ray_o,
+                  float *ray_d, float *near, float *far, int32_t *pixel, uint8_t *mask_at_box, int32_t *status,
+                  void *scratch, void *stream);
+
+/* ---------------------------------------------------------------------------------
  * nb_image_assemble — replaces the image re-assembly of the demo visualizer
  * (lib/visualizers/if_nerf_demo.py:15-30; same scatter in lib/evaluators/if_nerf.py:59-68):
  *   img = white_bkgd ? 1 : 0;  img[mask_at_box] = rgb_map;  (optionally) img = img[..., ::-1];  img *= scale

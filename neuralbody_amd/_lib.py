@@ -14,6 +14,7 @@ SLOT_DEAD = -2147483648  # NB_SLOT_DEAD
 PRECISIONS = {"f32": 0, "f16f6": 1}
 PACK_SECTIONS = {"f32": 1, "f16f6": 2}
 ILL_SIGMA, ILL_T_MIN = 4e-3, 1e-6  # NB_ILL_SIGMA, NB_ILL_T_MIN
+SAMPLE_MODES = {"h36m": 0, "plain": 1}  # NB_SAMPLE_H36M, NB_SAMPLE_PLAIN
 
 
 def ill_scratch_bytes(cap):
@@ -105,6 +106,9 @@ SIGNATURES = {
     "nb_enc_gather_codes": (C.c_int, [_P, _P, _P, _I32, _I32, _P, _P]),
     "nb_raygen": (C.c_int, [_I32, _I32, C.c_double * 9, C.c_double * 9, C.c_double * 3, C.c_float * 6, _P, _P, _P,
                             _P, _P, _P, _P, _P]),
+    "nb_train_rays_scratch_size": (_I64, [_I32, _I32]),
+    "nb_train_rays": (C.c_int, [_I32, _I32, C.c_double * 9, C.c_double * 9, C.c_double * 3, C.c_float * 6, _P, _I32, _P, _P,
+                                _I32, C.c_double, _P, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "nb_image_assemble": (C.c_int, [_P, _I64, _P, _P, _I64, C.c_int, C.c_int, C.c_float, _P, _P, _P, _P]),
     "nb_eval_metrics_scratch_size": (_I64, [_I32, _I32]),
     "nb_eval_metrics": (C.c_int, [_P, _I32, _I32, _P, _P, _I64, C.c_int, C.c_int, _P, _P, _P]),

@@ -569,6 +569,55 @@ def raygen(H, W, K, R, T, bounds, device):
     return ray_o, ray_d, near, far, mask, n_rays
 
 
+def train_rays_scratch(H, W, device):
+    """Scratch of nb_train_rays for an H x W image; ValueError for sizes the call refuses."""
+    n_bytes = int(_lib.lib().nb_train_rays_scratch_size(int(H), int(W)))
+    if n_bytes <= 0:
+        raise ValueError("train_rays: unsupported image size %d x %d (both >= 1, H*W <= 2^30)" % (H, W))
+    return torch.empty(n_bytes, dtype=torch.uint8, device=device)
+
+
+def train_rays(img, msk, K, R, T, bounds, hull, mode, body_ratio, u, scratch=None):
+    """nb_train_rays: img [H,W,3] fp32 and msk [H,W] uint8 device tensors; K, R [3,3], T [3] host float64; bounds [2,3] host
+    float32 (can_bounds); hull [n,2] host int (x, y), CCW (train_rays.bound_hull); mode 'h36m' | 'plain'; u [n_rounds, n_rays]
+    fp32 device uniforms.  Returns a dict of device tensors rgb, ray_o, ray_d [n_rays,3], near, far [n_rays], pixel [n_rays,2]
+    int32 (y, x), mask_at_box [n_rays] uint8 and status [4] int32 {n_filled, rounds_used, count_body, count_bound}.
+    Nothing is read back."""
+    import numpy as np
+
+    if mode not in _lib.SAMPLE_MODES:
+        raise ValueError("train_rays: mode must be one of %s, got %r" % (sorted(_lib.SAMPLE_MODES), mode))
+    _req(img, torch.float32, (None, None, 3), "img")
+    H, W = int(img.shape[0]), int(img.shape[1])
+    _req(msk, torch.uint8, (H, W), "msk")
+    _req(u, torch.float32, (None, None), "u")
+    dev = img.device
+    if msk.device != dev or u.device != dev:
+        raise ValueError("img, msk and u must share one device")
+    n_rounds, n = int(u.shape[0]), int(u.shape[1])
+    K = np.asarray(K, np.float64).reshape(9)
+    R = np.asarray(R, np.float64).reshape(9)
+    T = np.asarray(T, np.float64).reshape(3)
+    b = np.asarray(bounds, np.float32).reshape(6)
+    hull = np.ascontiguousarray(np.asarray(hull, np.int64).reshape(-1, 2))
+    if np.abs(hull).max(initial=0) >= 1 << 30:
+        raise ValueError("train_rays: hull coordinate with magnitude >= 2^30")
+    hull_c = (C.c_int32 * hull.size)(*[int(v) for v in hull.reshape(-1)])
+    if scratch is None:
+        scratch = train_rays_scratch(H, W, dev)
+    out = {"rgb": torch.empty((n, 3), dtype=torch.float32, device=dev), "ray_o": torch.empty((n, 3), dtype=torch.float32, device=dev),
+           "ray_d": torch.empty((n, 3), dtype=torch.float32, device=dev), "near": torch.empty(n, dtype=torch.float32, device=dev),
+           "far": torch.empty(n, dtype=torch.float32, device=dev), "pixel": torch.empty((n, 2), dtype=torch.int32, device=dev),
+           "mask_at_box": torch.empty(n, dtype=torch.uint8, device=dev), "status": torch.empty(4, dtype=torch.int32, device=dev)}
+    with torch.cuda.device(dev):
+        check(_lib.lib().nb_train_rays(H, W, (C.c_double * 9)(*K), (C.c_double * 9)(*R), (C.c_double * 3)(*T), (C.c_float * 6)(*b),
+                                       C.cast(hull_c, C.c_void_p), hull.shape[0], ptr(msk), ptr(img), _lib.SAMPLE_MODES[mode],
+                                       float(body_ratio), ptr(u), n_rounds, n, ptr(out["rgb"]), ptr(out["ray_o"]),
+                                       ptr(out["ray_d"]), ptr(out["near"]), ptr(out["far"]), ptr(out["pixel"]),
+                                       ptr(out["mask_at_box"]), ptr(out["status"]), ptr(scratch), _stream()), "nb_train_rays")
+    return out
+
+
 def image_assemble(mask_at_box, rgb_map, depth_map=None, white_bkgd=False, bgr=False, scale=1.0):
     """nb_image_assemble: mask_at_box [H*W] uint8/bool (any shape, flattened), rgb_map [n,3] and optional depth_map [n]
     in compacted pixel order -> (img [H*W,3], depth [H*W] or None) on device."""
