@@ -35,3 +35,4 @@ void nb_set_error(const char *fmt, ...);
     } while (0)
 
 static inline int nb_ceil_div(long long a, long long b) { return (int)((a + b - 1) / b); }
+static inline long long nb_align256(long long bytes) { return (bytes + 255) / 256 * 256; }  // scratch sections start 256-byte aligned

@@ -37,59 +37,43 @@ __global__ void vox_scatter_kernel(const int *__restrict__ coord, int n, Dims g,
     atomicMax(&grid[((long long)d * g.h + h) * g.w + w], v);  // last vertex wins
 }
 
-// Winners (the vertex a voxel kept) flagged and counted per 1024-vertex tile, then numbered in vertex order: the exclusive scan
-// folded into the kernels on either side of it (each block of the second sums the tile counts in front of it itself).  Two
-// kernels because the numbering overwrites the grid cells the flags are read from.
-__global__ __launch_bounds__(nbscan::BLOCK) void vox_flag_count_kernel(const int *__restrict__ coord, int n, Dims g,
-                                                                       const int *__restrict__ grid, int *__restrict__ flags,
-                                                                       int *__restrict__ block_sums) {
-    const int v0 = blockIdx.x * nbscan::TILE + threadIdx.x * nbscan::ITEMS;
-    int s = 0;
-#pragma unroll
-    for (int i = 0; i < nbscan::ITEMS; ++i) {
-        const int v = v0 + i;
-        if (v >= n) break;
+// Winners (the vertex a voxel kept) flagged and counted per 1024-vertex tile, then numbered in vertex order: the tile body of
+// nb_scan_dev.h on two sequences.  The count pass computes and stores the winner flag and the place pass reads it, because the
+// numbering overwrites the grid cells the flag is derived from.
+struct VoxWinners {  // count pass
+    const int *__restrict__ coord, *__restrict__ grid;
+    Dims g;
+    int *__restrict__ flags;
+    __device__ __forceinline__ int value(long long i) const {
+        const int v = (int)i;
         const int d = coord[v * 3], h = coord[v * 3 + 1], w = coord[v * 3 + 2];
         int f = 0;
         if ((unsigned)d < (unsigned)g.d && (unsigned)h < (unsigned)g.h && (unsigned)w < (unsigned)g.w)
             f = grid[((long long)d * g.h + h) * g.w + w] == v;
         flags[v] = f;
-        s += f;
+        return f;
     }
-    int tot;
-    nbscan::block_excl_scan(s, &tot);
-    if (threadIdx.x == 0) block_sums[blockIdx.x] = tot;
-}
+};
 
-__global__ __launch_bounds__(nbscan::BLOCK) void vox_number_kernel(const int *__restrict__ coord, int n, Dims g,
-                                                                   const int *__restrict__ flags, const int *__restrict__ block_sums,
-                                                                   int *__restrict__ grid, int *__restrict__ rows_vert,
-                                                                   int *__restrict__ rows_lin, int *__restrict__ n_rows) {
-    const int before = nbscan::blocks_before(block_sums, blockIdx.x);
-    const int v0 = blockIdx.x * nbscan::TILE + threadIdx.x * nbscan::ITEMS;
-    int f[nbscan::ITEMS], s = 0;
-#pragma unroll
-    for (int i = 0; i < nbscan::ITEMS; ++i) {
-        f[i] = v0 + i < n ? flags[v0 + i] : 0;
-        s += f[i];
-    }
-    int tot;
-    int r = nbscan::block_excl_scan(s, &tot) + before;
-#pragma unroll
-    for (int i = 0; i < nbscan::ITEMS; ++i) {
-        if (!f[i]) continue;
-        const int v = v0 + i;
+struct VoxRows {  // place pass
+    const int *__restrict__ coord, *__restrict__ flags;
+    Dims g;
+    int *__restrict__ grid, *__restrict__ rows_vert, *__restrict__ rows_lin, *__restrict__ n_rows;
+    __device__ __forceinline__ int value(long long i) const { return flags[i]; }
+    __device__ __forceinline__ void place(long long i, int winner, int r) const {
+        if (!winner) return;
+        const int v = (int)i;
         const int d = coord[v * 3], h = coord[v * 3 + 1], w = coord[v * 3 + 2];
         const int lin = (d * g.h + h) * g.w + w;
         rows_vert[r] = v;
         rows_lin[r] = lin;
         grid[lin] = r;
-        ++r;
     }
-    if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) *n_rows = before + tot;
-}
+    __device__ __forceinline__ void total(int t) const { *n_rows = t; }
+};
 
 // ------------------------------------------------------------------ strided-conv output index set
+// mark, then the marked cells counted per 1024-cell tile and numbered in linear order: nbscan::MarkedGrid through the tile body
 __global__ void down_mark_kernel(const int *__restrict__ in_lin, const int *__restrict__ n_in, Dims gi, Dims go,
                                  int *__restrict__ out_grid) {
     const int r = blockIdx.x * blockDim.x + threadIdx.x;
@@ -103,43 +87,6 @@ __global__ void down_mark_kernel(const int *__restrict__ in_lin, const int *__re
             for (int c = 0; c < 1 + (x & 1); ++c)
                 if (oz[a] < go.d && oy[b] < go.h && ox[c] < go.w)
                     out_grid[((long long)oz[a] * go.h + oy[b]) * go.w + ox[c]] = 0;  // mark (any value >= 0)
-}
-
-// Marked cells counted per 1024-cell tile, then numbered in linear order (row id into the cell, the cell into out_lin, the count
-// clamped to the capacity): the scan folded into its neighbours as above; a cell is read and rewritten by one thread only.
-__global__ __launch_bounds__(nbscan::BLOCK) void grid_count_kernel(const int *__restrict__ grid, long long n,
-                                                                   int *__restrict__ block_sums) {
-    const long long i0 = (long long)blockIdx.x * nbscan::TILE + threadIdx.x * nbscan::ITEMS;
-    int s = 0;
-#pragma unroll
-    for (int i = 0; i < nbscan::ITEMS; ++i)
-        if (i0 + i < n) s += grid[i0 + i] >= 0;
-    int tot;
-    nbscan::block_excl_scan(s, &tot);
-    if (threadIdx.x == 0) block_sums[blockIdx.x] = tot;
-}
-
-__global__ __launch_bounds__(nbscan::BLOCK) void grid_number_kernel(int *__restrict__ grid, long long n,
-                                                                    const int *__restrict__ block_sums, int cap,
-                                                                    int *__restrict__ out_lin, int *__restrict__ n_out) {
-    const int before = nbscan::blocks_before(block_sums, blockIdx.x);
-    const long long i0 = (long long)blockIdx.x * nbscan::TILE + threadIdx.x * nbscan::ITEMS;
-    int f[nbscan::ITEMS], s = 0;
-#pragma unroll
-    for (int i = 0; i < nbscan::ITEMS; ++i) {
-        f[i] = i0 + i < n ? grid[i0 + i] >= 0 : 0;
-        s += f[i];
-    }
-    int tot;
-    int r = nbscan::block_excl_scan(s, &tot) + before;
-#pragma unroll
-    for (int i = 0; i < nbscan::ITEMS; ++i) {
-        if (!f[i]) continue;
-        grid[i0 + i] = r < cap ? r : -1;
-        if (r < cap) out_lin[r] = (int)(i0 + i);
-        ++r;
-    }
-    if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) *n_out = min(before + tot, cap);
 }
 
 // ------------------------------------------------------------------ the index sets of ALL strided levels in three launches
@@ -178,41 +125,20 @@ __device__ __forceinline__ int down_all_level(const DownAll &a) {  // (block-uni
     return l;
 }
 
-__global__ __launch_bounds__(nbscan::BLOCK) void grid_count_all_kernel(DownAll a, int *__restrict__ block_sums) {
-    const int l = down_all_level(a);
-    const int *grid = a.grid[l];
-    const long long n = a.nvox[l], i0 = (long long)((int)blockIdx.x - a.tile0[l]) * nbscan::TILE + threadIdx.x * nbscan::ITEMS;
-    int s = 0;
-#pragma unroll
-    for (int i = 0; i < nbscan::ITEMS; ++i)
-        if (i0 + i < n) s += grid[i0 + i] >= 0;
-    int tot;
-    nbscan::block_excl_scan(s, &tot);
-    if (threadIdx.x == 0) block_sums[blockIdx.x] = tot;
+__device__ __forceinline__ nbscan::MarkedGrid down_all_cells(const DownAll &a, int l) {
+    return {a.grid[l], a.out_lin[l], a.n_out[l], a.cap[l]};
 }
 
-__global__ __launch_bounds__(nbscan::BLOCK) void grid_number_all_kernel(DownAll a, const int *__restrict__ block_sums) {
-    const int l = down_all_level(a), tile = (int)blockIdx.x - a.tile0[l];
-    int *grid = a.grid[l];
-    const long long n = a.nvox[l], i0 = (long long)tile * nbscan::TILE + threadIdx.x * nbscan::ITEMS;
-    const int cap = a.cap[l];
-    const int before = nbscan::blocks_before(block_sums + a.tile0[l], tile);
-    int f[nbscan::ITEMS], s = 0;
-#pragma unroll
-    for (int i = 0; i < nbscan::ITEMS; ++i) {
-        f[i] = i0 + i < n ? grid[i0 + i] >= 0 : 0;
-        s += f[i];
-    }
-    int tot;
-    int r = nbscan::block_excl_scan(s, &tot) + before;
-#pragma unroll
-    for (int i = 0; i < nbscan::ITEMS; ++i) {
-        if (!f[i]) continue;
-        grid[i0 + i] = r < cap ? r : -1;
-        if (r < cap) a.out_lin[l][r] = (int)(i0 + i);
-        ++r;
-    }
-    if ((int)blockIdx.x == a.tile0[l + 1] - 1 && threadIdx.x == 0) *a.n_out[l] = min(before + tot, cap);
+// the tile body on the level's grid; a level's tile sums start at tile_sums[tile0 of the level], its last tile writes its count
+__global__ __launch_bounds__(nbscan::BLOCK) void grid_count_all_kernel(DownAll a, int *__restrict__ tile_sums) {
+    const int l = down_all_level(a);
+    nbscan::tile_count(down_all_cells(a, l), a.nvox[l], (int)blockIdx.x - a.tile0[l], tile_sums + a.tile0[l]);
+}
+
+__global__ __launch_bounds__(nbscan::BLOCK) void grid_place_all_kernel(DownAll a, const int *__restrict__ tile_sums) {
+    const int l = down_all_level(a), tile = (int)blockIdx.x - a.tile0[l], tiles_of_level = a.tile0[l + 1] - a.tile0[l];
+    const int before = nbscan::blocks_before(tile_sums + a.tile0[l], tile);
+    nbscan::tile_place(down_all_cells(a, l), a.nvox[l], tile, before, tile == tiles_of_level - 1);
 }
 
 // ------------------------------------------------------------------ sparse 3x3x3 convolution
@@ -893,15 +819,12 @@ int nb_enc_voxelize(const int32_t *coord, int32_t n_verts, const int32_t dhw[3],
         NB_HIP(hipMemsetAsync(n_rows, 0, sizeof(int), st));
         return NB_OK;
     }
-    int *flags, *pos, *bs;
-    nb_scan_carve(scratch, n_verts, &flags, &pos, &bs);
-    (void)pos;
-    const dim3 tiles((unsigned)nb_scan_blocks(n_verts)), blk(nbscan::BLOCK);
+    int *flags, *bs;
+    nb_scan_carve(scratch, n_verts, &flags, nullptr, &bs);
     hipLaunchKernelGGL(vox_scatter_kernel, dim3(nb_ceil_div(n_verts, 256)), dim3(256), 0, st, coord, n_verts, g, grid);
-    hipLaunchKernelGGL(vox_flag_count_kernel, tiles, blk, 0, st, coord, n_verts, g, grid, flags, bs);
-    hipLaunchKernelGGL(vox_number_kernel, tiles, blk, 0, st, coord, n_verts, g, flags, bs, grid, rows_vert, rows_lin, n_rows);
-    NB_CHECK_LAUNCH("nb_enc_voxelize");
-    return NB_OK;
+    const VoxWinners winners = {coord, grid, g, flags};
+    const VoxRows rows = {coord, flags, g, grid, rows_vert, rows_lin, n_rows};
+    return nbscan::count_and_place("nb_enc_voxelize", winners, rows, n_verts, bs, st);
 }
 
 int nb_enc_downsample_index(const int32_t *in_lin, const int32_t *n_in, int32_t n_in_max, const int32_t in_dhw[3],
@@ -917,17 +840,13 @@ int nb_enc_downsample_index(const int32_t *in_lin, const int32_t *n_in, int32_t 
     hipStream_t st = (hipStream_t)stream;
     const long long nvox = (long long)go.d * go.h * go.w;
     if (!(flags & NB_GRID_PREFILLED)) NB_HIP(hipMemsetAsync(out_grid, 0xFF, nvox * sizeof(int), st));
-    int *fl, *pos, *bs;
-    nb_scan_carve(scratch, nvox, &fl, &pos, &bs);
+    int *bs;
+    nb_scan_carve(scratch, nvox, nullptr, nullptr, &bs);
     if (n_in_max > 0)
         hipLaunchKernelGGL(down_mark_kernel, dim3(nb_ceil_div(n_in_max, 256)), dim3(256), 0, st, in_lin, n_in, gi, go,
                            out_grid);
-    (void)fl, (void)pos;
-    const dim3 tiles((unsigned)nb_scan_blocks(nvox)), blk(nbscan::BLOCK);
-    hipLaunchKernelGGL(grid_count_kernel, tiles, blk, 0, st, out_grid, nvox, bs);
-    hipLaunchKernelGGL(grid_number_kernel, tiles, blk, 0, st, out_grid, nvox, bs, n_out_max, out_lin, n_out);
-    NB_CHECK_LAUNCH("nb_enc_downsample_index");
-    return NB_OK;
+    const nbscan::MarkedGrid cells = {out_grid, out_lin, n_out, n_out_max};
+    return nbscan::count_and_place("nb_enc_downsample_index", cells, cells, nvox, bs, st);
 }
 
 int nb_enc_downsample_index_all(const int32_t *in_lin, const int32_t *n_in, int32_t n_in_max, const int32_t in_dhw[3], int32_t n_levels,
@@ -956,16 +875,15 @@ int nb_enc_downsample_index_all(const int32_t *in_lin, const int32_t *n_in, int3
     // the tiles' sums of all levels lie in the flags area of a scratch sized for the first level: nb_scan_scratch_size(max(cells of
     // level 1, 64)) — a level of more than one tile has > 1024 cells, so n_levels <= 4 tiles or far fewer tiles than cells
     const long long scratch_cells = nvox1 > 64 ? nvox1 : 64;
-    int *fl, *pos, *bs;
-    nb_scan_carve(scratch, scratch_cells, &fl, &pos, &bs);
-    (void)pos, (void)bs;
+    int *fl;
+    nb_scan_carve(scratch, scratch_cells, &fl, nullptr, nullptr);
     NB_REQUIRE(a.tile0[n_levels] <= scratch_cells, "nb_enc_downsample_index_all: %d tiles for a scratch of %lld ints", a.tile0[n_levels], scratch_cells);
     const Dims gi = {in_dhw[0], in_dhw[1], in_dhw[2]};
     if (n_in_max > 0)
         hipLaunchKernelGGL(down_mark_all_kernel, dim3(nb_ceil_div(n_in_max, 256)), dim3(256), 0, st, in_lin, n_in, gi, a);
     const dim3 tiles((unsigned)a.tile0[n_levels]), blk(nbscan::BLOCK);
     hipLaunchKernelGGL(grid_count_all_kernel, tiles, blk, 0, st, a, fl);
-    hipLaunchKernelGGL(grid_number_all_kernel, tiles, blk, 0, st, a, fl);
+    hipLaunchKernelGGL(grid_place_all_kernel, tiles, blk, 0, st, a, fl);
     NB_CHECK_LAUNCH("nb_enc_downsample_index_all");
     return NB_OK;
 }

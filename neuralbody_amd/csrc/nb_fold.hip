@@ -9,6 +9,7 @@
 // nb_sparsify derives the active set of a dense volume that came without one.
 #include "nb_march_common.h"
 #include "nb_scan.h"
+#include "nb_scan_dev.h"
 
 typedef _Float16 f16x8v __attribute__((ext_vector_type(8)));
 
@@ -137,7 +138,8 @@ __global__ __launch_bounds__(256, 2) void nb_fold_rows_kernel(FoldArgs a) {
 }
 
 // ---------------------------------------------------------------- active set of a dense volume
-__global__ void sparsify_flag_kernel(const float *__restrict__ vol, long long nvox, int c, int *__restrict__ flags) {
+// active voxels marked in the grid (0, any value >= 0; -1 otherwise) for nbscan::MarkedGrid to count and number
+__global__ void sparsify_mark_kernel(const float *__restrict__ vol, long long nvox, int c, int *__restrict__ grid) {
     const long long v = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (v >= nvox) return;
     const f32x4 *p = reinterpret_cast<const f32x4 *>(vol + v * c);
@@ -146,17 +148,7 @@ __global__ void sparsify_flag_kernel(const float *__restrict__ vol, long long nv
         const f32x4 x = p[q];
         any = any || x.x != 0.f || x.y != 0.f || x.z != 0.f || x.w != 0.f;
     }
-    flags[v] = any ? 1 : 0;
-}
-__global__ void sparsify_assign_kernel(const int *__restrict__ flags, const int *__restrict__ pos, long long nvox, int cap,
-                                       int *__restrict__ grid, int *__restrict__ rows_lin, int *__restrict__ n_rows) {
-    const long long v = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (v == 0) *n_rows = min(*n_rows, cap);  // the scan wrote the grand total here
-    if (v >= nvox) return;
-    const int p = pos[v];
-    const bool on = flags[v] != 0 && p < cap;
-    grid[v] = on ? p : -1;
-    if (on) rows_lin[p] = (int)v;
+    grid[v] = any ? 0 : -1;
 }
 
 }  // namespace
@@ -206,14 +198,11 @@ int nb_sparsify(const float *vol, const int32_t dhw[3], int32_t c, int32_t *grid
     const long long nvox = (long long)dhw[0] * dhw[1] * dhw[2];
     NB_REQUIRE(nvox >= 1 && nvox < (1ll << 31), "nb_sparsify: %lld voxels", nvox);
     hipStream_t st = (hipStream_t)stream;
-    int *flags, *pos, *bsum;
-    nb_scan_carve(scratch, nvox, &flags, &pos, &bsum);
-    const int nb = nb_ceil_div(nvox, 256);
-    hipLaunchKernelGGL(sparsify_flag_kernel, dim3(nb), dim3(256), 0, st, vol, nvox, c, flags);
-    if (int rc = nb_exclusive_scan(flags, pos, n_rows, nvox, bsum, st)) return rc;
-    hipLaunchKernelGGL(sparsify_assign_kernel, dim3(nb), dim3(256), 0, st, flags, pos, nvox, n_rows_max, grid, rows_lin, n_rows);
-    NB_CHECK_LAUNCH("nb_sparsify");
-    return NB_OK;
+    int *bsum;
+    nb_scan_carve(scratch, nvox, nullptr, nullptr, &bsum);
+    hipLaunchKernelGGL(sparsify_mark_kernel, dim3(nb_ceil_div(nvox, 256)), dim3(256), 0, st, vol, nvox, c, grid);
+    const nbscan::MarkedGrid cells = {grid, rows_lin, n_rows, n_rows_max};
+    return nbscan::count_and_place("nb_sparsify", cells, cells, nvox, bsum, st);
 }
 
 }  // extern "C"

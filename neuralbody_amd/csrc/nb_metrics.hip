@@ -260,7 +260,6 @@ __global__ __launch_bounds__(BLOCK) void metrics_final_kernel(const double *__re
 
 constexpr long long MAX_PIXELS = 1LL << 30;  // int32 positions and flag sums of the scan
 
-inline long long align256(long long v) { return (v + 255) / 256 * 256; }
 inline long long flag_blocks(long long n) { return (n + PIX_PER_BLOCK - 1) / PIX_PER_BLOCK; }
 inline long long ssim_tiles(int H, int W) { return (long long)nb_ceil_div(W, TILE_W) * nb_ceil_div(H, TILE_H); }
 
@@ -270,7 +269,7 @@ extern "C" int64_t nb_eval_metrics_scratch_size(int32_t H, int32_t W) {
     if (H < 1 || W < 1 || (long long)H * W > MAX_PIXELS) return 0;
     const long long n = (long long)H * W;
     // [scan: flags | positions | block sums] [box 4 x int32] [mse partials] [ssim partials] [whole-image mse partials]  (fp64)
-    return align256(nb_scan_scratch_size(n)) + 256 + align256(8 * flag_blocks(n)) + 2 * align256(8 * ssim_tiles(H, W));
+    return nb_align256(nb_scan_scratch_size(n)) + 256 + nb_align256(8 * flag_blocks(n)) + 2 * nb_align256(8 * ssim_tiles(H, W));
 }
 
 extern "C" int nb_eval_metrics(const uint8_t *mask_at_box, int32_t H, int32_t W, const float *rgb_pred, const float *rgb_gt,
@@ -283,14 +282,14 @@ extern "C" int nb_eval_metrics(const uint8_t *mask_at_box, int32_t H, int32_t W,
     const long long n = (long long)H * W;
     int *flags, *pos, *bs;
     nb_scan_carve(scratch, n, &flags, &pos, &bs);
-    char *p = static_cast<char *>(scratch) + align256(nb_scan_scratch_size(n));
+    char *p = static_cast<char *>(scratch) + nb_align256(nb_scan_scratch_size(n));
     int *box = reinterpret_cast<int *>(p);
     p += 256;
     const int n_fb = (int)flag_blocks(n), n_tiles = (int)ssim_tiles(H, W);
     double *mse_part = reinterpret_cast<double *>(p);
-    p += align256(8LL * n_fb);
+    p += nb_align256(8LL * n_fb);
     double *ssim_part = reinterpret_cast<double *>(p);
-    p += align256(8LL * n_tiles);
+    p += nb_align256(8LL * n_tiles);
     double *wmse_part = reinterpret_cast<double *>(p);
 
     const long long n_elem = 3 * (long long)n_rays;
@@ -298,8 +297,8 @@ extern "C" int nb_eval_metrics(const uint8_t *mask_at_box, int32_t H, int32_t W,
     NB_HIP(hipMemsetAsync(box, 0, 4 * sizeof(int), st));
     hipLaunchKernelGGL(metrics_flag_kernel, dim3(n_fb), dim3(BLOCK), 0, st, mask_at_box, H, W, flags, box, rgb_pred, rgb_gt,
                        n_elem, chunk, mse_part);
-    // the total lands in the block-sum area's spare slot: nobody needs it on the host
-    if (int rc = nb_exclusive_scan(flags, pos, bs + nb_scan_blocks(n), n, bs, st)) return rc;
+    // nobody needs the total on the host
+    if (int rc = nb_exclusive_scan(flags, pos, nb_scan_total_slot(bs, n), n, bs, st)) return rc;
     hipLaunchKernelGGL(metrics_ssim_kernel, dim3(nb_ceil_div(W, TILE_W), nb_ceil_div(H, TILE_H)), dim3(BLOCK), 0, st,
                        mask_at_box, pos, H, W, rgb_pred, rgb_gt, (long long)n_rays, white_bkgd ? 1.f : 0.f, whole_img ? 1 : 0,
                        box, ssim_part, wmse_part);

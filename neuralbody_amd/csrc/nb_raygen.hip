@@ -104,8 +104,8 @@ extern "C" int nb_image_assemble(const uint8_t *mask_at_box, int64_t n_pixels, c
     nb_scan_carve(scratch, n_pixels, &flags, &pos, &bs);
     const dim3 grd(nb_ceil_div(n_pixels, 256)), blk(256);
     hipLaunchKernelGGL(mask_flag_kernel, grd, blk, 0, st, mask_at_box, (long long)n_pixels, flags);
-    // the total lands in the block-sum area's spare slot: nobody needs it on the host
-    if (int rc = nb_exclusive_scan(flags, pos, bs + nb_scan_blocks(n_pixels), n_pixels, bs, st)) return rc;
+    // nobody needs the total on the host
+    if (int rc = nb_exclusive_scan(flags, pos, nb_scan_total_slot(bs, n_pixels), n_pixels, bs, st)) return rc;
     hipLaunchKernelGGL(image_assemble_kernel, grd, blk, 0, st, flags, pos, (long long)n_pixels, (long long)n_rays, rgb_map,
                        depth_map, white_bkgd ? 1.f : 0.f, bgr, scale, img, depth);
     NB_CHECK_LAUNCH("nb_image_assemble");

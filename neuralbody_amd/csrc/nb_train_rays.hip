@@ -190,8 +190,8 @@ extern "C" int nb_train_rays(int32_t H, int32_t W, const double K[9], const doub
     int *f_body, *pos_body, *bs_body, *f_bound, *pos_bound, *bs_bound;
     nb_scan_carve(scratch, n, &f_body, &pos_body, &bs_body);
     nb_scan_carve(static_cast<char *>(scratch) + nb_scan_scratch_size(n), n, &f_bound, &pos_bound, &bs_bound);
-    // the two totals stay on the device, in the spare slot behind each class's block sums
-    int *n_body = bs_body + nb_scan_blocks(n), *n_bound = bs_bound + nb_scan_blocks(n);
+    // the two totals stay on the device
+    int *n_body = nb_scan_total_slot(bs_body, n), *n_bound = nb_scan_total_slot(bs_bound, n);
     hipLaunchKernelGGL(classify_kernel, dim3(nb_ceil_div(n, 256)), dim3(256), 0, st, h, H, W, mode, msk, f_body, f_bound);
     if (int rc = nb_exclusive_scan(f_body, pos_body, n_body, n, bs_body, st)) return rc;
     if (int rc = nb_exclusive_scan(f_bound, pos_bound, n_bound, n, bs_bound, st)) return rc;

@@ -151,8 +151,9 @@ def test_points_on_every_marching_tier_match_the_fp32_kernel(kind):
 
 
 def test_sparsify_beyond_the_two_kernel_scan():
-    """More than 4 Mi voxels: nb_exclusive_scan takes its three-kernel form (the block totals get their own pass); a handful of
-    non-zero voxels at known places, in linear order."""
+    """More than 4 Mi voxels = more than 4096 tiles: count, place and between them the pass over the tile totals (nb_scan_tops; the
+    three-kernel form of nbscan::count_and_place, here on the marked grid); a handful of non-zero voxels at known places, in linear
+    order."""
     from neuralbody_amd import ops
 
     D, H, W, C = 66, 256, 256, 32  # 4.3 Mi voxels
