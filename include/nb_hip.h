@@ -537,6 +537,37 @@ int nb_marching_cubes_count(const float *cube, const int32_t dims[3], float iso,
 int nb_marching_cubes_emit(const float *cube, const int32_t dims[3], float iso, float *vertices, int32_t *triangles,
                            int32_t vert_cap, int32_t tri_cap, void *scratch, void *stream);
 
+/* ---------------------------------------------------------------------------------
+ * The query lattice of the mesh pass on device — replaces the per-item host work of
+ * lib/datasets/light_stage/multi_view_mesh_dataset.py (get_mask :102-115, prepare_inside_pts :117-140, the meshgrid of
+ * __getitem__ :150-158) and the boolean indexing around calculate_density in lib/networks/renderer/if_mesh_renderer.py:30-46.
+ *   A lattice is three DEVICE fp32 axis vectors ax [X], ay [Y], az [Z] and dims = {X, Y, Z} (host): point (i, j, k) =
+ *   (ax[i], ay[j], az[k]), linear index (i*Y + j)*Z + k — np.meshgrid(x, y, z, indexing='ij') (:157) without the [X,Y,Z,3]
+ *   array.  Every side >= 1, X*Y*Z <= 2^31 - 1, else NB_EINVAL.  scratch dev: nb_scan_scratch_size(X*Y*Z) bytes.
+ *   No atomics, no synchronisation: the same inputs give the same bits.
+ * nb_mask_dilate — cv2.dilate(msk, np.ones((border, border), np.uint8)) of get_mask (:111-113) for n_views masks at once:
+ *   out[v,y,x] = max of msk[v] over the border x border window centred on (y, x); pixels outside the image are ignored
+ *   (cv2's default border value for dilation); border odd, 1..255 (1 copies).  msk, out dev [n_views,H,W] uint8, distinct.
+ * nb_lattice_carve — prepare_inside_pts (:117-140): inside[p] = 1 iff point p projects onto a non-zero pixel of every view's
+ *   mask, else 0.  The projection, the rounding (half to even), the clamp to the image and the treatment of non-finite pixel
+ *   coordinates are those of nb_cull in nb_march (one device function serves both); cull->pre_affine must be 0.
+ *   cull HOST pointer, its members DEVICE pointers; inside dev [X*Y*Z] uint8 out; n_inside dev [1] int32 out = the flag sum.
+ * nb_lattice_gather — pts[inside] (if_mesh_renderer.py:30-31) of ANY bitmap (non-zero = flagged), in linear order:
+ *   wpts dev [cap,3] fp32 = the flagged points' coordinates (the axis values, bit for bit), lin dev [cap] int32 = their linear
+ *   indices (np.flatnonzero(inside)); flagged points beyond cap are dropped and nothing is written behind row min(total, cap);
+ *   n_out dev [2] int32 = {min(total, cap), total}.  cap = 0 only counts (wpts, lin may be NULL).
+ * nb_lattice_scatter — cube[inside] = alpha; np.pad(cube, pad) (if_mesh_renderer.py:42-46) in one step: cube dev
+ *   [X+2*pad, Y+2*pad, Z+2*pad] fp32, ZEROED BY THE CALLER; cube[i+pad, j+pad, k+pad] = alpha[r * alpha_stride] for the point
+ *   (i, j, k) = lin[r], r < n (n <= X*Y*Z; an entry of lin that is no lattice point writes nothing).  alpha_stride in floats:
+ *   1 for the [1,n,1] tensor of calculate_density. */
+int nb_mask_dilate(const uint8_t *msk, int32_t n_views, int32_t H, int32_t W, int32_t border, uint8_t *out, void *stream);
+int nb_lattice_carve(const float *ax, const float *ay, const float *az, const int32_t dims[3], const nb_cull *cull,
+                     uint8_t *inside, int32_t *n_inside, void *scratch, void *stream);
+int nb_lattice_gather(const float *ax, const float *ay, const float *az, const int32_t dims[3], const uint8_t *inside,
+                      int32_t cap, float *wpts, int32_t *lin, int32_t *n_out, void *scratch, void *stream);
+int nb_lattice_scatter(const float *alpha, int64_t alpha_stride, const int32_t *lin, int64_t n, const int32_t dims[3],
+                       int32_t pad, float *cube, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

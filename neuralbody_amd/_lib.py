@@ -115,6 +115,10 @@ SIGNATURES = {
     "nb_marching_cubes_scratch_size": (_I64, [_I32x3]),
     "nb_marching_cubes_count": (C.c_int, [_P, _I32x3, C.c_float, _P, _P, _P]),
     "nb_marching_cubes_emit": (C.c_int, [_P, _I32x3, C.c_float, _P, _P, _I32, _I32, _P, _P]),
+    "nb_mask_dilate": (C.c_int, [_P, _I32, _I32, _I32, _I32, _P, _P]),
+    "nb_lattice_carve": (C.c_int, [_P, _P, _P, _I32x3, C.POINTER(NbCull), _P, _P, _P, _P]),
+    "nb_lattice_gather": (C.c_int, [_P, _P, _P, _I32x3, _P, _I32, _P, _P, _P, _P, _P]),
+    "nb_lattice_scatter": (C.c_int, [_P, _I64, _P, _I64, _I32x3, _I32, _P, _P]),
 }
 
 _lib = None

@@ -960,3 +960,115 @@ def make_cull(masks, RT, K, R0=None, Th0=None):
         c.snap = snap.data_ptr()
         keep.append(snap)
     return c, keep
+
+
+# ------------------------------------------------------------------------------------------- the mesh pass's query lattice
+def _lattice(axes):
+    """(ax, ay, az) device fp32 vectors -> (dims, number of points); ValueError for lattices the calls refuse."""
+    if len(axes) != 3:
+        raise ValueError("a lattice is three axis vectors, got %d" % len(axes))
+    for name, a in zip(("axis_x", "axis_y", "axis_z"), axes):
+        _req(a, torch.float32, (None,), name)
+    dims = [int(a.shape[0]) for a in axes]
+    n = dims[0] * dims[1] * dims[2]
+    if min(dims) < 1 or n > 2 ** 31 - 1:
+        raise ValueError("lattice %s: every side >= 1 and at most 2^31 - 1 points" % (dims,))
+    if len(set(a.device for a in axes)) != 1:
+        raise ValueError("the three axes live on different devices")
+    return dims, n
+
+
+def lattice_scratch(dims, device):
+    """Scratch of lattice_carve / lattice_gather for an [X,Y,Z] lattice."""
+    return scan_scratch(int(dims[0]) * int(dims[1]) * int(dims[2]), device)
+
+
+def mask_dilate(masks, border=5, out=None):
+    """nb_mask_dilate: cv2.dilate(m, ones((border, border))) of every mask of a device uint8 [V,H,W] stack -> a new [V,H,W]."""
+    _req(masks, torch.uint8, (None, None, None), "masks")
+    border = int(border)
+    if border < 1 or border % 2 == 0 or border > 255:
+        raise ValueError("border must be odd, 1..255, got %d" % border)
+    if masks.numel() == 0:
+        raise ValueError("masks is empty: %s" % (tuple(masks.shape),))
+    if out is None:
+        out = torch.empty_like(masks)
+    _req(out, torch.uint8, tuple(masks.shape), "out")
+    V, H, W = (int(v) for v in masks.shape)
+    with torch.cuda.device(masks.device):
+        check(_lib.lib().nb_mask_dilate(ptr(masks), V, H, W, border, ptr(out), _stream()), "nb_mask_dilate")
+    return out
+
+
+def lattice_carve(axes, cull, scratch=None, inside=None, n_inside=None):
+    """nb_lattice_carve: axes = (ax [X], ay [Y], az [Z]) device fp32, cull = the NbCull of make_cull (whose keepalive the caller
+    holds) -> (inside [X,Y,Z] uint8, n_inside [1] int32), device tensors; nothing is read back."""
+    dims, n = _lattice(axes)
+    dev = axes[0].device
+    if not isinstance(cull, NbCull):
+        raise TypeError("cull must be the NbCull of ops.make_cull")
+    if inside is None:
+        inside = torch.empty(dims, dtype=torch.uint8, device=dev)
+    if n_inside is None:
+        n_inside = torch.empty(1, dtype=torch.int32, device=dev)
+    _req(inside, torch.uint8, tuple(dims), "inside")
+    _req(n_inside, torch.int32, (1,), "n_inside")
+    if scratch is None:
+        scratch = lattice_scratch(dims, dev)
+    with torch.cuda.device(dev):
+        check(_lib.lib().nb_lattice_carve(ptr(axes[0]), ptr(axes[1]), ptr(axes[2]), _i3(dims), C.byref(cull), ptr(inside),
+                                          ptr(n_inside), ptr(scratch), _stream()), "nb_lattice_carve")
+    return inside, n_inside
+
+
+def lattice_gather(axes, inside, wpts=None, lin=None, scratch=None, n_out=None):
+    """nb_lattice_gather: the flagged points of a device uint8 bitmap [X,Y,Z] in linear order into wpts [cap,3] fp32 and
+    lin [cap] int32 (both None: count only) -> n_out, a [2] int32 device tensor {min(total, cap), total}; nothing is read back."""
+    dims, n = _lattice(axes)
+    dev = axes[0].device
+    _req(inside, torch.uint8, tuple(dims), "inside")
+    if (wpts is None) != (lin is None):
+        raise ValueError("wpts and lin come together")
+    cap = 0
+    if wpts is not None:
+        _req(wpts, torch.float32, (None, 3), "wpts")
+        cap = min(int(wpts.shape[0]), 2 ** 31 - 1)
+        _req(lin, torch.int32, (int(wpts.shape[0]),), "lin")
+    if n_out is None:
+        n_out = torch.empty(2, dtype=torch.int32, device=dev)
+    _req(n_out, torch.int32, (2,), "n_out")
+    if scratch is None:
+        scratch = lattice_scratch(dims, dev)
+    with torch.cuda.device(dev):
+        check(_lib.lib().nb_lattice_gather(ptr(axes[0]), ptr(axes[1]), ptr(axes[2]), _i3(dims), ptr(inside), cap, ptr(wpts),
+                                           ptr(lin), ptr(n_out), ptr(scratch), _stream()), "nb_lattice_gather")
+    return n_out
+
+
+def lattice_scatter(alpha, lin, dims, pad, cube=None):
+    """nb_lattice_scatter: alpha (device fp32 with n elements along ONE dimension, any stride: the [1,n,1] of calculate_density,
+    or a column of a wider tensor) at the lattice points lin [n] int32 -> cube [X+2*pad, Y+2*pad, Z+2*pad] fp32, 0 elsewhere
+    (a `cube` of the caller's must be zeroed)."""
+    if not isinstance(alpha, torch.Tensor):
+        raise TypeError("alpha must be a torch.Tensor")
+    if not alpha.is_cuda:
+        raise NbError("alpha must live on a HIP device (got %s); the HIP path has no CPU fallback" % (alpha.device,))
+    if alpha.dtype != torch.float32:
+        raise ValueError("alpha must be torch.float32, got %s" % (alpha.dtype,))
+    _req(lin, torch.int32, (None,), "lin")
+    n = int(lin.shape[0])
+    long_dims = [d for d in range(alpha.dim()) if alpha.shape[d] != 1]
+    if alpha.numel() != n or len(long_dims) > 1:
+        raise ValueError("alpha has shape %s, expected %d elements along one dimension" % (tuple(alpha.shape), n))
+    stride = int(alpha.stride(long_dims[0])) if long_dims else 1
+    if stride < 1:
+        raise ValueError("alpha has stride %d" % stride)
+    dims, pad = [int(d) for d in dims], int(pad)
+    shape = tuple(d + 2 * pad for d in dims)
+    if cube is None:
+        cube = torch.zeros(shape, dtype=torch.float32, device=alpha.device)
+    _req(cube, torch.float32, shape, "cube")
+    with torch.cuda.device(alpha.device):
+        check(_lib.lib().nb_lattice_scatter(ptr(alpha), stride, ptr(lin), n, _i3(dims), pad, ptr(cube), _stream()),
+              "nb_lattice_scatter")
+    return cube

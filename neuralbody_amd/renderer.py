@@ -437,7 +437,8 @@ class RendererMesh(Renderer):
     lattice point flagged `inside`) runs on HIP in ONE nb_decode_points launch (the reference chunks 131 072 points per
     call, :37).  Marching cubes (:46-52) runs on the device too (`extract_mesh`: nb_marching_cubes on the fp32 cube, which is
     never downloaded); `render` keeps the reference's host post-processing (PyMCubes, trimesh) wherever PyMCubes imports and
-    cfg.mesh_backend does not say "device"."""
+    cfg.mesh_backend does not say "device".  The lattice itself comes from the dataset: the reference's `pts` and `inside`, or
+    the three axes and the device-carved `inside` of neuralbody_amd/mesh_lattice.py."""
 
     PAD = 10  # np.pad(cube, 10), if_mesh_renderer.py:46
 
@@ -446,7 +447,11 @@ class RendererMesh(Renderer):
         return torch.cat([alpha_decoder(wpts[:, i:i + chunk]) for i in range(0, wpts.shape[1], chunk)], 1)
 
     def density_cube(self, batch, pad=PAD):
-        """-> DEVICE float32 tensor [X+2*pad, Y+2*pad, Z+2*pad]: alpha at the inside lattice points, 0 elsewhere."""
+        """-> DEVICE float32 tensor [X+2*pad, Y+2*pad, Z+2*pad]: alpha at the inside lattice points, 0 elsewhere.
+        A batch that carries the lattice's axes (`axis_x`, `axis_y`, `axis_z`: neuralbody_amd/mesh_lattice.py) never holds the
+        [X,Y,Z,3] points: see `_density_cube_axes`.  A batch with `pts` is the reference dataset's."""
+        if "axis_x" in batch:
+            return self._density_cube_axes(batch, pad)
         pts = batch["pts"]
         inside = batch["inside"][0].bool()
         wpts = pts[0][inside][None].contiguous()
@@ -457,12 +462,43 @@ class RendererMesh(Renderer):
         cube[inside] = alpha[0, :, 0]
         return torch.nn.functional.pad(cube, (pad,) * 6)
 
+    @staticmethod
+    def _axes(batch):
+        """The lattice's three axis vectors of a collated batch (batch size 1, like `pts[0]` above)."""
+        axes = [batch[k] for k in ("axis_x", "axis_y", "axis_z")]
+        if any(a.dim() != 2 or a.shape[0] != 1 for a in axes):
+            raise ValueError("axis_x / axis_y / axis_z must be [1, n] (test.batch_size 1), got %s" % (
+                [tuple(a.shape) for a in axes],))
+        return [a[0].contiguous() for a in axes]
+
+    def _density_cube_axes(self, batch, pad):
+        """nb_lattice_gather -> calculate_density -> nb_lattice_scatter into the padded cube.  The count pass of the gather runs
+        first (cap 0) and its 8-byte `n_out` is the one read-back: it sizes the point list, like `pts[0][inside]` does."""
+        axes = self._axes(batch)
+        inside = batch["inside"][0]
+        inside = (inside if inside.dtype == torch.uint8 else (inside != 0).to(torch.uint8)).contiguous()
+        dims = [int(a.shape[0]) for a in axes]
+        scratch = ops.lattice_scratch(dims, inside.device)
+        total = int(ops.lattice_gather(axes, inside, scratch=scratch)[1].item())
+        if total == 0:  # nothing to decode: the zero cube
+            return torch.zeros([d + 2 * pad for d in dims], dtype=torch.float32, device=inside.device)
+        wpts = torch.empty((total, 3), dtype=torch.float32, device=inside.device)
+        lin = torch.empty(total, dtype=torch.int32, device=inside.device)
+        ops.lattice_gather(axes, inside, wpts, lin, scratch=scratch)
+        sp_input = self.prepare_sp_input(batch)
+        feature_volume = self.net.encode_sparse_voxels(sp_input)
+        alpha = self.net.calculate_density(wpts[None], feature_volume, sp_input)
+        return ops.lattice_scatter(alpha, lin, dims, pad)
+
     def _to_world(self, vertices, batch, pad=PAD):
         """Lattice index units of the padded cube -> world units: (v - pad) * step + wbounds[0] (the two lines the reference
         leaves commented out, if_mesh_renderer.py:49-50, with the step read from the lattice instead of the literal 0.005)."""
-        pts = batch["pts"]
-        step = torch.stack([pts[0, 1, 0, 0, 0] - pts[0, 0, 0, 0, 0], pts[0, 0, 1, 0, 1] - pts[0, 0, 0, 0, 1],
-                            pts[0, 0, 0, 1, 2] - pts[0, 0, 0, 0, 2]]).to(vertices)
+        if "pts" in batch:
+            pts = batch["pts"]
+            step = torch.stack([pts[0, 1, 0, 0, 0] - pts[0, 0, 0, 0, 0], pts[0, 0, 1, 0, 1] - pts[0, 0, 0, 0, 1],
+                                pts[0, 0, 0, 1, 2] - pts[0, 0, 0, 0, 2]]).to(vertices)
+        else:
+            step = torch.stack([a[1] - a[0] for a in self._axes(batch)]).to(vertices)
         return (vertices - float(pad)) * step + batch["wbounds"][0, 0].to(vertices)
 
     def extract_mesh(self, batch, world=False, cube=None):

@@ -1,0 +1,134 @@
+"""Host side of the mesh lattice (neuralbody_amd/mesh_lattice.py) against tests/golden/mesh_lattice.npz, which the unmodified
+reference dataset wrote (tests/golden/make_golden_mesh_lattice.py): the axes, the two restatements of prepare_inside_pts the
+GPU tests lean on, and the dataset's host item.  Nothing here touches a device."""
+import os
+import types
+
+import numpy as np
+import pytest
+
+from tests import lattice_ref as lr
+
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "mesh_lattice.npz")
+BAND_MAX = 0.03  # of the lattice
+
+
+@pytest.fixture(scope="module")
+def gold():
+    with np.load(GOLDEN) as z:
+        return {k: z[k] for k in z.files}
+
+
+def _source(gold, n_items=1):
+    from neuralbody_amd.mesh_lattice import MemoryMeshSource
+
+    item = (gold["msks_raw"], gold["xyz"], gold["Rh"], gold["Th"])
+    return MemoryMeshSource([item] * n_items, gold["Ks"], gold["Rs"], gold["Ts"])
+
+
+def _cfg(**kw):
+    from neuralbody_amd.mesh_lattice import MeshLatticeConfig
+
+    return MeshLatticeConfig(voxel_size=(0.02, 0.02, 0.02), **kw)
+
+
+def test_lattice_axes_are_the_references_bits(gold):
+    from neuralbody_amd.mesh_lattice import lattice_axes
+
+    axes = lattice_axes(gold["wbounds"], [float(v) for v in gold["voxel_size"]])
+    for a, name in zip(axes, ("axis_x", "axis_y", "axis_z")):
+        assert a.dtype == np.float32 and a.shape == gold[name].shape
+        assert np.array_equal(a.view(np.uint32), gold[name].view(np.uint32)), name
+    assert [len(a) for a in axes] == [24, 36, 15]
+    with pytest.raises(ValueError):
+        lattice_axes(gold["wbounds"].astype(np.float64), (0.02, 0.02, 0.02))  # another dtype gives other bits
+    with pytest.raises(ValueError):
+        lattice_axes(gold["wbounds"], (0.02, 0.0, 0.02))
+
+
+def test_the_two_restatements_agree_outside_the_band(gold):
+    axes = [gold["axis_x"], gold["axis_y"], gold["axis_z"]]
+    RT = np.concatenate([gold["Rs"], gold["Ts"]], axis=2)
+    assert np.array_equal(lr.dilate(gold["msks_raw"], 5), gold["msks_dilated"])
+    band = lr.near_band(axes, gold["msks_dilated"], gold["Ks"], RT)
+    f32 = lr.inside(axes, gold["msks_dilated"], gold["Ks"], RT, "f32")
+    f64 = lr.inside(axes, gold["msks_dilated"], gold["Ks"], RT, "f64")
+    ref = gold["inside"]
+    print("band %.2f %% of %d points; f32 != f64 at %d, reference != f64 at %d (all inside the band: %s)" % (
+        100.0 * band.mean(), band.size, int((f32 != f64).sum()), int((ref != f64).sum()),
+        not ((f32 != f64) & ~band).any() and not ((ref != f64) & ~band).any()))
+    assert band.mean() <= BAND_MAX
+    assert ref.dtype == np.uint8 and ref.shape == (24, 36, 15) and 0 < ref.sum() < ref.size
+    assert np.array_equal(f32[~band], f64[~band])
+    assert np.array_equal(ref[~band], f64[~band])
+
+
+def test_dilate_restatement_on_a_hand_case():
+    m = np.zeros((1, 5, 7), np.uint8)
+    m[0, 0, 0], m[0, 4, 6], m[0, 2, 3] = 1, 9, 4
+    d3 = lr.dilate(m, 3)[0]
+    assert d3[:2, :2].tolist() == [[1, 1], [1, 1]] and d3[3:, 5:].tolist() == [[9, 9], [9, 9]]
+    assert (d3[1:4, 2:5] == 4).all() and d3[0, 2] == 0 and d3.sum() == 4 * 1 + 4 * 9 + 9 * 4
+    assert np.array_equal(lr.dilate(m, 1), m)
+
+
+def test_host_item_is_the_references_item(gold):
+    from neuralbody_amd.mesh_lattice import MeshLatticeDataset
+
+    ds = MeshLatticeDataset(_source(gold, 3), _cfg(begin_ith_frame=4, num_train_frame=2), device="cpu")
+    assert len(ds) == 3
+    it = ds.host_item(0)
+    # multi_view_mesh_dataset.py:162-178 without pts / inside, plus the axes and the raw masks
+    assert set(it) == {"coord", "out_sh", "wbounds", "bounds", "R", "Th", "latent_index", "frame_index", "axis_x", "axis_y",
+                       "axis_z", "msks"}
+    for k, ref in (("coord", gold["coord"]), ("out_sh", gold["out_sh"]), ("wbounds", gold["wbounds"]), ("bounds", gold["bounds"]),
+                   ("R", gold["R"]), ("Th", gold["Th_item"]), ("axis_x", gold["axis_x"]), ("msks", gold["msks_raw"])):
+        assert it[k].dtype == ref.dtype and it[k].shape == ref.shape, (k, it[k].dtype, ref.dtype, it[k].shape, ref.shape)
+        assert np.array_equal(it[k], ref), k
+    assert (it["latent_index"], it["frame_index"]) == (0, 4)
+    assert [(ds.host_item(i)["latent_index"], ds.host_item(i)["frame_index"]) for i in (1, 2)] == [(1, 5), (1, 6)]
+    assert "pts" not in it
+    with pytest.raises(ValueError, match="masks"):
+        from neuralbody_amd.mesh_lattice import MemoryMeshSource
+
+        bad = MemoryMeshSource([(gold["msks_raw"][:2], gold["xyz"], gold["Rh"], gold["Th"])], gold["Ks"], gold["Rs"], gold["Ts"])
+        MeshLatticeDataset(bad, _cfg(), device="cpu").host_item(0)
+
+
+def test_the_device_ops_refuse_host_tensors(gold):
+    """No CPU fallback: the item itself (and `pts` with it) cannot be made without a device."""
+    import torch
+
+    from neuralbody_amd import ops
+    from neuralbody_amd.mesh_lattice import MeshLatticeDataset
+
+    with pytest.raises(ops.NbError):
+        ops.mask_dilate(torch.zeros((1, 4, 4), dtype=torch.uint8), 5)
+    axes = [torch.zeros(3), torch.zeros(2), torch.zeros(2)]
+    with pytest.raises(ops.NbError):
+        ops.lattice_gather(axes, torch.zeros((3, 2, 2), dtype=torch.uint8))
+    with pytest.raises(ops.NbError):
+        ops.lattice_scatter(torch.zeros(2), torch.zeros(2, dtype=torch.int32), (3, 2, 2), 1)
+    with pytest.raises(ops.NbError):
+        MeshLatticeDataset(_source(gold), _cfg(mesh_lattice_pts=True), device="cpu")[0]
+
+
+def test_plugin_binds_the_live_cfg_and_refuses_workers(gold):
+    from tests import helpers as H
+    from neuralbody_amd.mesh_lattice import MeshLatticeDataset
+
+    cfg = types.SimpleNamespace(begin_ith_frame=2, num_train_frame=3, num_render_frame=-1, voxel_size=[0.02, 0.02, 0.02],
+                                big_box=False, training_view=[0, 1, 2], train=types.SimpleNamespace(num_workers=0),
+                                test=types.SimpleNamespace(batch_size=1))
+    mod = H.load_plugin("light_stage_mesh_dataset.py", cfg)
+    ds = mod.Dataset("nowhere", "CoreView_313", "none.npy", "test", source=_source(gold, 2))
+    assert isinstance(ds, MeshLatticeDataset) and len(ds) == 2
+    assert (ds.cfg.begin_ith_frame, ds.cfg.num_train_frame, ds.cfg.big_box, ds.cfg.mesh_lattice_pts) == (2, 3, False, False)
+    cfg.mesh_lattice_pts, cfg.big_box = True, True  # read at call time
+    assert (ds.cfg.mesh_lattice_pts, ds.cfg.big_box) == (True, True)
+    cfg.train.num_workers = 8
+    with pytest.raises(ValueError, match="num_workers"):
+        mod.Dataset("nowhere", "CoreView_313", "none.npy", "test", source=_source(gold))
+    cfg.train.num_workers, cfg.test.batch_size = 0, 2
+    with pytest.raises(ValueError, match="batch_size"):
+        mod.Dataset("nowhere", "CoreView_313", "none.npy", "test", source=_source(gold))
