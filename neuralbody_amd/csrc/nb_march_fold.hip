@@ -28,7 +28,8 @@
 //           ds_read_b64_tr_b16 transposes into K-major A fragments, conflict-free                  [behind the last MFMA phase]
 //   Wt      owner lanes zero their samples' B-fragment slots and scatter the 8 corner weights of their level (head and
 //           remainder, ATen's corner order and zero padding: a corner outside the volume writes nothing)             [same place]
-//   MFMA    per 16-voxel chunk and wave: 2 x 2 tiles x 3 products.
+//   MFMA    per 16-voxel chunk and wave: 2 x 2 tiles x 3 products — LIVE chunks only: a chunk without an active voxel (all sixteen
+//           entries the zero row) is neither fetched nor multiplied (live_chunks)
 // A list longer than 128 voxels is marched in passes of 128 over the same boxes (up to 1024 voxels: neighbouring but not dense
 // points, wide pixel footprints); beyond that (rays far apart: small images, random rays) in sample groups of 16 or, failing
 // that, one sample at a time through the very same steps (K = 32 for a single sample).
@@ -608,23 +609,51 @@ __device__ __forceinline__ void lvl_store(char *actz, const Prep &p, int tid, in
     if (tid == 0) *reinterpret_cast<int *>(actz + HDR_OFF) = p.K;
 }
 
-// the K list of the step about to be marched, per wave: chunks, the wave's U region (R chunk slots behind the Wt chunks)
+// The LIVE chunks of the table in LDS (wave-uniform, bit c = chunk c): a chunk whose 16 entries are all the zero row adds exact
+// zeros to the accumulators, so neither its U rows are fetched nor its MFMAs issued.  Lane l compares entries 2 l and 2 l + 1
+// (entries at or beyond 16 nch are stale: they do not count); one ballot, whose 8-lane groups collapse to a bit each on the
+// scalar unit.  The table is complete at the barrier in front of the first caller and untouched until fold_mfma has run.
+__device__ __forceinline__ unsigned live_chunks(const char *actz, int lane, int nch, unsigned zero_off) {
+    typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+    const u32x2 e = reinterpret_cast<const u32x2 *>(actz + TBL_OFF)[lane];
+    const unsigned long long b = __builtin_amdgcn_ballot_w64(lane < 8 * nch && (e.x != zero_off || e.y != zero_off));
+    // any bit of a byte -> the byte's bit 0; bits 0, 8, 16, 24 of a half -> bits 21 .. 24 of its product with 2^21 + 2^14 + 2^7 + 1
+    auto half = [](unsigned x) -> unsigned {
+        x |= x >> 4;
+        x |= x >> 2;
+        x |= x >> 1;
+        return ((x & 0x01010101u) * 0x00204081u >> 21) & 0xfu;
+    };
+    return half((unsigned)b) | half((unsigned)(b >> 32)) << 4;
+}
+__device__ __forceinline__ int pop_chunk(unsigned &m) {  // lowest live chunk of m, taken out of it
+    const int c = __builtin_ctz(m);
+    m &= m - 1u;
+    return c;
+}
+
+// the K list of the step about to be marched, per wave: chunks, the live ones among them, the wave's U region (R chunk slots behind
+// the Wt chunks: its place is a function of the list's length alone, R shrinks to the number of live chunks)
 struct UCfg {
     int nch, R;
+    unsigned live;  // bit c: chunk c has an active voxel
+    int n_live;
     unsigned ring;  // LDS byte address of the wave's region
     int ring_off;   // the same as an offset into the workgroup's LDS
 };
-__device__ __forceinline__ UCfg ucfg_k(int K, unsigned lds_base, int wave);
-__device__ __forceinline__ UCfg ucfg(const char *actz, unsigned lds_base, int wave) {
-    return ucfg_k(__builtin_amdgcn_readfirstlane(*reinterpret_cast<const int *>(actz + HDR_OFF)), lds_base, wave);
-}
-__device__ __forceinline__ UCfg ucfg_k(int K, unsigned lds_base, int wave) {
+__device__ __forceinline__ UCfg ucfg_k(int K, unsigned live, unsigned lds_base, int wave) {
     UCfg u;
     u.nch = (K + 15) >> 4;
-    u.R = u.nch <= 3 ? u.nch : (u.nch == 4 ? 3 : 2);  // (64 KiB - 4 KiB nch) / (4 waves x 4 KiB)
-    u.ring_off = WT_CHUNK * u.nch + wave * u.R * U_CHUNK;
+    const int r = u.nch <= 3 ? u.nch : (u.nch == 4 ? 3 : 2);  // (64 KiB - 4 KiB nch) / (4 waves x 4 KiB)
+    u.live = live;
+    u.n_live = __builtin_popcount(live);
+    u.R = min(r, u.n_live);
+    u.ring_off = WT_CHUNK * u.nch + wave * r * U_CHUNK;
     u.ring = lds_base + (unsigned)u.ring_off;
     return u;
+}
+__device__ __forceinline__ int list_len(const char *actz) {
+    return __builtin_amdgcn_readfirstlane(*reinterpret_cast<const int *>(actz + HDR_OFF));
 }
 // One chunk (16 voxels) of this wave's 64 features, heads and remainders: 4 LDS-DMA instructions of 64 lanes x 16 bytes.  The
 // image per (form, M tile) KiB is [4 voxel groups][2 feature halves][4 voxels][16 features]: lane s fetches 8 features
@@ -653,7 +682,8 @@ __device__ __forceinline__ void dma_chunk(const MarchArgs &a, const char *actz, 
         }
 }
 __device__ __forceinline__ void dma_initial(const MarchArgs &a, const char *actz, int lane, int wave, const UCfg &u) {
-    for (int c = 0; c < u.R; ++c) dma_chunk(a, actz, lane, wave, c, u.ring + c * U_CHUNK);  // R <= nch
+    unsigned rest = u.live;
+    for (int c = 0; c < u.R; ++c) dma_chunk(a, actz, lane, wave, pop_chunk(rest), u.ring + c * U_CHUNK);  // R <= n_live
 }
 __device__ __forceinline__ void dma_wait() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 
@@ -710,7 +740,8 @@ __device__ __forceinline__ f16x8 tr_frag(const char *p) {
     typedef short s8v __attribute__((ext_vector_type(8)));
     return __builtin_bit_cast(f16x8, s8v{a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]});
 }
-// acc += U^T . Wt over the step's K list: per chunk 4 A fragments (2 tiles x heads, remainders) and 4 B fragments feed 12 MFMAs.
+// acc += U^T . Wt over the LIVE chunks of the step's K list, in ascending order (c counts them: ring slots and waits go by c, the
+// table entries and the Wt fragment by the chunk's place in the list): per chunk 4 A fragments (2 tiles x heads, remainders) and 4 B fragments feed 12 MFMAs.
 // Software-pipelined: the fragments of chunk c + 1 are read from LDS (and, beyond the R resident chunks, its DMA awaited with
 // a COUNTED vmcnt: 4 instructions per younger chunk) before the MFMAs of chunk c are issued; the slot of chunk c is refilled
 // with chunk c + R as soon as its reads have returned.
@@ -747,37 +778,39 @@ __device__ __forceinline__ void fold_mma(const FoldFrags &f, f32x16 (&acc)[2][2]
 }
 __device__ __forceinline__ void fold_mfma(const MarchArgs &a, char *actz, int lane, int wave, const UCfg &u, f32x16 (&acc)[2][2],
                                           unsigned *tbuf = nullptr) {
-    if (u.nch == 0) return;  // uniform
+    if (u.n_live == 0) return;  // uniform: no active voxel in the whole list (or an empty list)
     FOLD_SUB(17);
     const int l15 = lane & 15, g4 = lane >> 4;
     const int tro = (g4 >> 1) * 512 + (g4 & 1) * 128 + (l15 >> 2) * 32 + (l15 & 3) * 8;
     const char *wt = actz + lane * 16;
     const char *ring = actz + u.ring_off + tro;
     int issued = u.R - 1;  // highest chunk whose DMA has been issued
+    unsigned to_read = u.live, to_fetch = u.live;  // live chunks not yet read / not yet requested
+    for (int c = 0; c < u.R; ++c) to_fetch &= to_fetch - 1u;
     FoldFrags f0, f1;
     fold_wait(issued);
     FOLD_SUB(18);
-    fold_read(f0, ring, wt);
+    fold_read(f0, ring, wt + pop_chunk(to_read) * WT_CHUNK);
     NB_HOOK_FOLD_FIRST_READ(f0);
     FOLD_SUB(19);
     auto step = [&](FoldFrags &cur, FoldFrags &nxt, int c, int slot) {
-        if (c + u.R < u.nch) {  // uniform: refill this chunk's slot; its reads must have returned
+        if (c + u.R < u.n_live) {  // uniform: refill this chunk's slot; its reads must have returned
             asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(cur.ah[0]), "+v"(cur.ah[1]), "+v"(cur.al[0]), "+v"(cur.al[1])::"memory");
-            dma_chunk(a, actz, lane, wave, c + u.R, u.ring + slot * U_CHUNK);
+            dma_chunk(a, actz, lane, wave, pop_chunk(to_fetch), u.ring + slot * U_CHUNK);
             issued = c + u.R;
         }
-        if (c + 1 < u.nch) {
+        if (c + 1 < u.n_live) {
             const int ns = slot + 1 == u.R ? 0 : slot + 1;
             fold_wait(issued - (c + 1));
-            fold_read(nxt, ring + ns * U_CHUNK, wt + (c + 1) * WT_CHUNK);
+            fold_read(nxt, ring + ns * U_CHUNK, wt + pop_chunk(to_read) * WT_CHUNK);
         }
         fold_mma(cur, acc);
     };
     int slot = 0;
-    for (int c = 0; c < u.nch; c += 2) {
+    for (int c = 0; c < u.n_live; c += 2) {
         step(f0, f1, c, slot);
         slot = slot + 1 == u.R ? 0 : slot + 1;
-        if (c + 1 < u.nch) {
+        if (c + 1 < u.n_live) {
             step(f1, f0, c + 1, slot);
             slot = slot + 1 == u.R ? 0 : slot + 1;
         }
@@ -785,7 +818,7 @@ __device__ __forceinline__ void fold_mfma(const MarchArgs &a, char *actz, int la
 #pragma unroll
     for (int m = 0; m < 2; ++m) asm volatile("" : "+v"(acc[m][0]), "+v"(acc[m][1]));
     FOLD_SUB(20);
-    if (tbuf && lane == 0) tbuf[21] = (unsigned)u.nch;
+    if (tbuf && lane == 0) tbuf[21] = (unsigned)u.n_live;
 }
 
 // compositing state of the weights output: 16 consecutive depth steps of a ray = 64 bytes, 4 steps per owner lane
@@ -1013,7 +1046,8 @@ __global__ __launch_bounds__(256, 2) void nb_march_fold_kernel(MarchArgs a, cons
     auto fetch_and_weights = [&](int lane_c) {
         if (tier == 0 && active) {
             const int os = lane_c & 15, part = lane_c >> 4;
-            const UCfg u = ucfg(lds, lds_base, wave);
+            const int K = list_len(lds);
+            const UCfg u = ucfg_k(K, live_chunks(lds, lane_c, (K + 15) >> 4, a.fold.zero_off), lds_base, wave);
             dma_initial(a, lds, lane_c, wave, u);
             const Lvl lv = load_lvl(lds, part);
             wt_build(lds, lv, g, ins, wave, os, part, u.nch);
@@ -1045,17 +1079,19 @@ __global__ __launch_bounds__(256, 2) void nb_march_fold_kernel(MarchArgs a, cons
             // ---- fc_0 folded into the volume: H1_pre = b0 + U^T . Wt over the step's voxel list
             init_bias<2>(pk + P_B0, 2 * wave, hi, acc);
             if (tier == 0) {
-                const UCfg u = ucfg(actz, lds_base, wave);
+                const int K = list_len(actz);
+                const UCfg u = ucfg_k(K, live_chunks(actz, lane_i, (K + 15) >> 4, a.fold.zero_off), lds_base, wave);
                 fold_mfma(a, actz, lane_i, wave, u, acc, NB_HOOK_TBUF);
             } else if (tier == 3) {
                 // a list of up to KM_CAP voxels (points that are neighbours but not dense, wide pixel footprints): the same boxes,
                 // marched in passes of K_CAP voxels, each through table -> U -> Wt -> MFMA
                 const Lvl lv = load_lvl(actz, part);
-                const int K = __builtin_amdgcn_readfirstlane(*reinterpret_cast<const int *>(actz + HDR_OFF));
+                const int K = list_len(actz);
                 for (int k_lo = 0; k_lo < K; k_lo += K_CAP) {
                     tbl_pass(actz, a.fold.zero_off, k_lo, K, tid);
                     __syncthreads();
-                    const UCfg u = ucfg_k(min(K - k_lo, K_CAP), lds_base, wave);
+                    const int kp = min(K - k_lo, K_CAP);
+                    const UCfg u = ucfg_k(kp, live_chunks(actz, lane_i, (kp + 15) >> 4, a.fold.zero_off), lds_base, wave);
                     dma_initial(a, actz, lane_i, wave, u);
                     wt_build(actz, lv, g, ins_cur, wave, os, part, u.nch, k_lo);
                     __syncthreads();
@@ -1075,7 +1111,8 @@ __global__ __launch_bounds__(256, 2) void nb_march_fold_kernel(MarchArgs a, cons
                     tbl_store(actz, tl, lv, a.fold.zero_off, pr.K, tid);
                     lvl_store(actz, pr, tid, os, part);
                     __syncthreads();
-                    const UCfg u = ucfg(actz, lds_base, wave);
+                    const int kg = list_len(actz);
+                    const UCfg u = ucfg_k(kg, live_chunks(actz, lane_i, (kg + 15) >> 4, a.fold.zero_off), lds_base, wave);
                     dma_initial(a, actz, lane_i, wave, u);
                     wt_build(actz, lv, g, take, wave, os, part, u.nch);
                     __syncthreads();
