@@ -568,6 +568,56 @@ int nb_lattice_gather(const float *ax, const float *ay, const float *az, const i
 int nb_lattice_scatter(const float *alpha, int64_t alpha_stride, const int32_t *lin, int64_t n, const int32_t dims[3],
                        int32_t pad, float *cube, void *stream);
 
+/* ---------------------------------------------------------------------------------
+ * A frame's geometry from SMPL parameters on device — replaces the offline vertex export of zju_smpl/extract_vertices.py
+ * (SMPLlayer.forward, zju_smpl/smplmodel/body_model.py:89-153, over lbs, zju_smpl/smplmodel/lbs.py:142-233, 280-378) and the
+ * per-frame prepare_input of lib/datasets/light_stage/multi_view_dataset.py:68-118 / monocular_dataset.py:32-71.
+ *   Plain fp32, no atomics, no allocation, no synchronisation: the same inputs give the same bits.
+ * nb_smpl_model — HOST struct, its arrays DEVICE fp32, laid out for the kernels (neuralbody_amd/smpl_pose.py::SmplModel):
+ *   v_template [3V]; shapedirs [10, 3V] (basis-major); posedirs [207, 3V] (the reference's own reshape, body_model.py:51; may be
+ *   NULL when new_params is never set); weights [24, V] (joint-major); j_template [24,3] = J_regressor . v_template and
+ *   j_shapedirs [24,3,10] = J_regressor . shapedirs, regressed once on the host; parents HOST [24], parents[0] = -1 and
+ *   0 <= parents[j] < j otherwise, else NB_EINVAL.
+ * nb_smpl_pose — params dev [F, NB_SMPL_PARAMS] fp32, one row per frame: poses 72 | shapes 10 | Rh 3 | Th 3 (the keys of
+ *   EasyMocap's params/{i}.npy).  verts dev [F,V,3] out: the world vertices body_model.py:148 returns (scale = 1); joints dev
+ *   [F,24,3] out or NULL: the posed joints (lbs.py:371) in the body's own frame.  new_params != 0 adds the pose blend shapes
+ *   (lbs.py:210-213); with 0 posedirs is never read.  batch_rodrigues is restated as written (angle = |r + 1e-8|, direction
+ *   r / angle, lbs.py:295-296).  Two sums are arranged so that the rest pose returns the shaped body exactly: the relative
+ *   transform's translation is accumulated along the chain as A_parent.t + G_parent.R (I - R_j) J_j (lbs.py:375-376 subtracts two
+ *   joint-sized numbers), and the blend is [I|0] + sum_j W[v,j] (A_j - [I|0]), which equals sum_j W[v,j] A_j (lbs.py:223) for
+ *   weights that sum to 1 per vertex.  ws dev [F, NB_SMPL_WS_FLOATS] fp32 scratch.  Two launches: one wave per frame (rotations,
+ *   joints, chain), then 64 vertices per workgroup, which reads every element of posedirs once per frame.
+ *   1 <= F <= 65535, V >= 1, else NB_EINVAL.
+ * nb_smpl_voxelize — prepare_input for verts dev [F,V,3] already on the device, one workgroup per frame.  Rh, Th dev: frame f's
+ *   three floats at Rh + f * rt_stride, Th + f * rt_stride (rt_stride in floats, >= 3: 3 for [F,3] arrays, NB_SMPL_PARAMS for the
+ *   columns of params).  voxel_size HOST [3] doubles in dhw order, each > 0 (cfg.voxel_size as Python floats).
+ *   pad_mode: NB_PAD_ZJU z -+ 0.05 (multi_view_dataset.py:80-81), NB_PAD_BIG_BOX all axes -+ 0.05 (:76-78), NB_PAD_SNAPSHOT
+ *   y -+ 0.1 (monocular_dataset.py:38-39), a float32 subtraction as numpy's on a float32 array; anything else NB_EINVAL.
+ *   R dev [F,3,3] out: cv2.Rodrigues(Rh) evaluated in double and rounded to fp32 (NOT the fp32 formula of the skinning step).
+ *   bounds dev [F,2,3] out: padded min / max of (v - Th) . R in fp32.  coord dev [F,V,3] int32 out, dhw order:
+ *   int32(rint(double(dhw - min_dhw) / voxel_size)), the subtraction in fp32, rounding half to even (np.round, :111).
+ *   out_sh dev [F,3] int32 out: (int32(ceil(double(max_dhw - min_dhw) / voxel_size)) | 31) + 1 (:114-116).
+ *   summary dev [F,9] int32 out: the six fp32 of can_bounds (padded min / max of the world vertices, :73-83) bit-cast, then
+ *   out_sh — everything the host needs of a frame, in one 36-byte copy. */
+#define NB_SMPL_JOINTS 24
+#define NB_SMPL_POSE_BASIS 207
+#define NB_SMPL_BETAS 10
+#define NB_SMPL_PARAMS 88
+#define NB_SMPL_WS_FLOATS 512
+#define NB_PAD_ZJU 0
+#define NB_PAD_BIG_BOX 1
+#define NB_PAD_SNAPSHOT 2
+typedef struct nb_smpl_model {
+    int32_t n_verts;
+    int32_t parents[NB_SMPL_JOINTS];
+    const float *v_template, *shapedirs, *posedirs, *weights, *j_template, *j_shapedirs;
+} nb_smpl_model;
+int nb_smpl_pose(const nb_smpl_model *model, const float *params, int32_t n_frames, int new_params, float *ws, float *verts,
+                 float *joints, void *stream);
+int nb_smpl_voxelize(const float *verts, int32_t n_verts, int32_t n_frames, const float *Rh, const float *Th, int64_t rt_stride,
+                     const double voxel_size[3], int pad_mode, int32_t *coord, int32_t *out_sh, float *bounds, float *R,
+                     int32_t *summary, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,6 +15,8 @@ PRECISIONS = {"f32": 0, "f16f6": 1}
 PACK_SECTIONS = {"f32": 1, "f16f6": 2}
 ILL_SIGMA, ILL_T_MIN = 4e-3, 1e-6  # NB_ILL_SIGMA, NB_ILL_T_MIN
 SAMPLE_MODES = {"h36m": 0, "plain": 1}  # NB_SAMPLE_H36M, NB_SAMPLE_PLAIN
+PAD_MODES = {"zju": 0, "big_box": 1, "snapshot": 2}  # NB_PAD_ZJU, NB_PAD_BIG_BOX, NB_PAD_SNAPSHOT
+SMPL_JOINTS, SMPL_POSE_BASIS, SMPL_BETAS, SMPL_PARAMS, SMPL_WS_FLOATS = 24, 207, 10, 88, 512  # NB_SMPL_*
 
 
 def ill_scratch_bytes(cap):
@@ -50,6 +52,15 @@ class NbCull(C.Structure):
         ("msk", C.c_void_p),   # dev [n_views, H, W] uint8
         ("cam", C.c_void_p),   # dev [n_views, 21]: RT 3x4 | K 3x3
         ("snap", C.c_void_p),  # dev R0 (9) | Th0 (3) or NULL
+    ]
+
+
+class NbSmplModel(C.Structure):
+    _fields_ = [
+        ("n_verts", C.c_int32),
+        ("parents", C.c_int32 * SMPL_JOINTS),  # host
+        ("v_template", C.c_void_p), ("shapedirs", C.c_void_p), ("posedirs", C.c_void_p), ("weights", C.c_void_p),
+        ("j_template", C.c_void_p), ("j_shapedirs", C.c_void_p),  # dev
     ]
 
 
@@ -119,6 +130,8 @@ SIGNATURES = {
     "nb_lattice_carve": (C.c_int, [_P, _P, _P, _I32x3, C.POINTER(NbCull), _P, _P, _P, _P]),
     "nb_lattice_gather": (C.c_int, [_P, _P, _P, _I32x3, _P, _I32, _P, _P, _P, _P, _P]),
     "nb_lattice_scatter": (C.c_int, [_P, _I64, _P, _I64, _I32x3, _I32, _P, _P]),
+    "nb_smpl_pose": (C.c_int, [C.POINTER(NbSmplModel), _P, _I32, C.c_int, _P, _P, _P, _P]),
+    "nb_smpl_voxelize": (C.c_int, [_P, _I32, _I32, _P, _P, _I64, C.c_double * 3, C.c_int, _P, _P, _P, _P, _P, _P]),
 }
 
 _lib = None

@@ -7,7 +7,7 @@ import math
 import torch
 
 from . import _lib
-from ._lib import NbCull, NbError, NbFold, NbMlpParams, NbScene, check, ptr
+from ._lib import NbCull, NbError, NbFold, NbMlpParams, NbScene, NbSmplModel, check, ptr
 
 LEVEL_CHANNELS = (32, 64, 128, 128)
 DBG_WIDTH = 1600
@@ -1072,3 +1072,101 @@ def lattice_scatter(alpha, lin, dims, pad, cube=None):
         check(_lib.lib().nb_lattice_scatter(ptr(alpha), stride, ptr(lin), n, _i3(dims), pad, ptr(cube), _stream()),
               "nb_lattice_scatter")
     return cube
+
+
+# ------------------------------------------------------------------------------------------- a frame's geometry from SMPL parameters
+SMPL_MODEL_SHAPES = {"v_template": (None, 3), "shapedirs": (_lib.SMPL_BETAS, None), "posedirs": (_lib.SMPL_POSE_BASIS, None),
+                     "weights": (_lib.SMPL_JOINTS, None), "j_template": (_lib.SMPL_JOINTS, 3),
+                     "j_shapedirs": (_lib.SMPL_JOINTS, 3, _lib.SMPL_BETAS)}
+
+
+def make_smpl_model(arrays, parents):
+    """The nb_smpl_model of device fp32 arrays laid out as include/nb_hip.h says: v_template [V,3], shapedirs [10,3V], posedirs
+    [207,3V] (or None: a model for new_params = False only), weights [24,V], j_template [24,3], j_shapedirs [24,3,10], and the
+    host list `parents` [24] -> (NbSmplModel, keepalive list)."""
+    V = int(_req(arrays["v_template"], torch.float32, (None, 3), "v_template").shape[0])
+    if V < 1:
+        raise ValueError("the model has no vertices")
+    m, keep = NbSmplModel(), []
+    for name, shape in SMPL_MODEL_SHAPES.items():
+        t = arrays.get(name)
+        if t is None and name == "posedirs":
+            continue
+        shape = tuple(3 * V if s is None and name in ("shapedirs", "posedirs") else V if s is None else s for s in shape)
+        _req(t, torch.float32, shape, name)
+        if t.device != arrays["v_template"].device:
+            raise ValueError("%s lives on %s, v_template on %s" % (name, t.device, arrays["v_template"].device))
+        setattr(m, name, t.data_ptr())
+        keep.append(t)
+    parents = [int(v) for v in parents]
+    if len(parents) != _lib.SMPL_JOINTS or parents[0] != -1 or any(not 0 <= pa < j for j, pa in enumerate(parents) if j > 0):
+        raise ValueError("parents must be %d entries with parents[0] = -1 and 0 <= parents[j] < j, got %s" % (_lib.SMPL_JOINTS, parents))
+    m.n_verts = V
+    m.parents[:] = parents
+    return m, keep
+
+
+def smpl_pose(model, params, new_params=False, verts=None, joints=None, ws=None):
+    """nb_smpl_pose: model = the NbSmplModel of make_smpl_model (whose keepalive the caller holds), params device fp32 [F,88]
+    (poses 72 | shapes 10 | Rh 3 | Th 3 per frame) -> (verts [F,V,3], joints [F,24,3]) device fp32; nothing is read back."""
+    if not isinstance(model, NbSmplModel):
+        raise TypeError("model must be the NbSmplModel of ops.make_smpl_model")
+    _req(params, torch.float32, (None, _lib.SMPL_PARAMS), "params")
+    F, V, dev = int(params.shape[0]), int(model.n_verts), params.device
+    if not 1 <= F <= 65535:
+        raise ValueError("params holds %d frames (1 .. 65535 per call)" % F)
+    if new_params and not model.posedirs:
+        raise ValueError("new_params needs a model with posedirs")
+    if verts is None:
+        verts = torch.empty((F, V, 3), dtype=torch.float32, device=dev)
+    if joints is None:
+        joints = torch.empty((F, _lib.SMPL_JOINTS, 3), dtype=torch.float32, device=dev)
+    if ws is None:
+        ws = torch.empty((F, _lib.SMPL_WS_FLOATS), dtype=torch.float32, device=dev)
+    _req(verts, torch.float32, (F, V, 3), "verts")
+    _req(joints, torch.float32, (F, _lib.SMPL_JOINTS, 3), "joints")
+    _req(ws, torch.float32, (F, _lib.SMPL_WS_FLOATS), "ws")
+    with torch.cuda.device(dev):
+        check(_lib.lib().nb_smpl_pose(C.byref(model), ptr(params), F, 1 if new_params else 0, ptr(ws), ptr(verts), ptr(joints),
+                                      _stream()), "nb_smpl_pose")
+    return verts, joints
+
+
+def _rows3(t, F, name):
+    """A device fp32 [F,3] whose rows are contiguous (a column block of a wider row-major tensor included) -> its row stride."""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError("%s must be a torch.Tensor" % name)
+    if not t.is_cuda:
+        raise NbError("%s must live on a HIP device (got %s); the HIP path has no CPU fallback" % (name, t.device))
+    if t.dtype != torch.float32 or tuple(t.shape) != (F, 3) or t.stride(1) != 1 or (F > 1 and t.stride(0) < 3):
+        raise ValueError("%s must be float32 [%d,3] with contiguous rows, got %s %s strides %s" % (name, F, t.dtype, tuple(t.shape),
+                                                                                                t.stride()))
+    return int(t.stride(0)) if F > 1 else 3
+
+
+def smpl_voxelize(verts, Rh, Th, voxel_size, pad="zju"):
+    """nb_smpl_voxelize: verts device fp32 [F,V,3] (world), Rh, Th device fp32 [F,3] (contiguous rows, one common row stride),
+    voxel_size three Python floats (dhw), pad 'zju' | 'big_box' | 'snapshot' -> dict of device tensors coord [F,V,3] i32,
+    out_sh [F,3] i32, bounds [F,2,3], R [F,3,3] and summary [F,9] i32 (can_bounds' six floats bit-cast | out_sh)."""
+    _req(verts, torch.float32, (None, None, 3), "verts")
+    F, V, dev = int(verts.shape[0]), int(verts.shape[1]), verts.device
+    if F < 1 or V < 1:
+        raise ValueError("verts is empty: %s" % (tuple(verts.shape),))
+    s_rh, s_th = _rows3(Rh, F, "Rh"), _rows3(Th, F, "Th")
+    if s_rh != s_th:
+        raise ValueError("Rh and Th have different row strides (%d, %d)" % (s_rh, s_th))
+    if Rh.device != dev or Th.device != dev:
+        raise ValueError("verts, Rh and Th live on different devices")
+    if pad not in _lib.PAD_MODES:
+        raise ValueError("pad must be one of %s, got %r" % (sorted(_lib.PAD_MODES), pad))
+    vs = [float(v) for v in voxel_size]
+    if len(vs) != 3 or not all(0.0 < v < math.inf for v in vs):
+        raise ValueError("voxel_size must be three positive floats, got %r" % (voxel_size,))
+    out = {"coord": torch.empty((F, V, 3), dtype=torch.int32, device=dev), "out_sh": torch.empty((F, 3), dtype=torch.int32, device=dev),
+           "bounds": torch.empty((F, 2, 3), dtype=torch.float32, device=dev), "R": torch.empty((F, 3, 3), dtype=torch.float32, device=dev),
+           "summary": torch.empty((F, 9), dtype=torch.int32, device=dev)}
+    with torch.cuda.device(dev):
+        check(_lib.lib().nb_smpl_voxelize(ptr(verts), V, F, ptr(Rh), ptr(Th), s_rh, (C.c_double * 3)(*vs), _lib.PAD_MODES[pad],
+                                          ptr(out["coord"]), ptr(out["out_sh"]), ptr(out["bounds"]), ptr(out["R"]),
+                                          ptr(out["summary"]), _stream()), "nb_smpl_voxelize")
+    return out
