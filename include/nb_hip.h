@@ -618,6 +618,33 @@ int nb_smpl_voxelize(const float *verts, int32_t n_verts, int32_t n_frames, cons
                      const double voxel_size[3], int pad_mode, int32_t *coord, int32_t *out_sh, float *bounds, float *R,
                      int32_t *summary, void *stream);
 
+/* ---------------------------------------------------------------------------------
+ * nb_smpl_silhouette — cull masks of a pose that was never photographed: the posed body's triangles rasterised into the cull
+ * cameras on device.  The reference's novel-pose dataset reads the CIHP masks of real images from disk
+ * (lib/datasets/light_stage/multi_view_perform_dataset.py:105-127); the consumer is the sample cull of
+ * lib/networks/renderer/if_clight_renderer_mmsk.py:12-45 (nb_cull in nb_march), whose round -> clamp lookup fixes the pixel
+ * convention here.  No allocation, no synchronisation; the output is a function of the inputs alone (the same bits every call).
+ *   verts dev [F,V,3] fp32 (nb_smpl_pose); faces dev [Nf,3] int32 vertex indices, either winding (a face with an index outside
+ *   0..V-1 is skipped; neuralbody_amd/smpl_pose.py::SmplModel validates the list once on the host); cam dev [nv,21] fp32, the
+ *   layout of nb_cull.cam (RT 3x4 | K 3x3).  out dev [F,nv,H,W] uint8, 1 = body; a dirty buffer is fine.
+ *   Projection: p = R v + T, (u, w) = (K p).xy / (K p).z in fp32, nb_cull's operations in nb_cull's order.  u, w are snapped to 1/256
+ *   pixel (rintf(256 u), half to even) and held as integers.  Pixel (x, y) is the closed unit square centred on the integer
+ *   point (x, y).  Coverage is conservative and exact: a pixel is set for a triangle iff its square meets the closed snapped
+ *   triangle — the square overlaps the triangle's bounding box and, with the triangle oriented to positive area, every int64
+ *   edge function satisfies E_i(pixel centre) + 128 (|dx_i| + |dy_i|) >= 0 (1/256 units).  A snapped triangle of zero area is
+ *   skipped.  The mask is the union over the triangles.
+ *   A (frame, view) with any vertex at camera depth (R v + T).z < 0.01 m, or projecting beyond +-32768 px (or to a NaN),
+ *   does not cull: its mask is all 1.  The other views of the call are unaffected.  (The bound keeps every product below 2^48.)
+ *   1 <= F <= 65535, V, Nf >= 1, 1 <= nv <= NB_MAX_CULL_VIEWS, F nv V and F nv Nf < 2^31 - 256, 1 <= H, W <= 32768, else
+ *   NB_EINVAL.  scratch dev, 16-byte aligned: nb_smpl_silhouette_scratch_size(F, V, Nf, nv) bytes (0 for refused dimensions).
+ *   Five stream operations: a memset of the scratch header, the projection, a fill (0, or 1 for a view that does not cull), one
+ *   thread per (frame, view, triangle) that walks a clipped bounding box of at most 16 x 16 pixels, and a fixed grid that gives
+ *   each larger triangle a workgroup (their list and its count stay in the scratch). */
+int64_t nb_smpl_silhouette_scratch_size(int32_t n_frames, int32_t n_verts, int32_t n_faces, int32_t n_views);
+int nb_smpl_silhouette(const float *verts, const int32_t *faces, const float *cam, int32_t n_frames, int32_t n_verts,
+                       int32_t n_faces, int32_t n_views, int32_t H, int32_t W, void *scratch, int64_t scratch_bytes, uint8_t *out,
+                       void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -132,6 +132,8 @@ SIGNATURES = {
     "nb_lattice_scatter": (C.c_int, [_P, _I64, _P, _I64, _I32x3, _I32, _P, _P]),
     "nb_smpl_pose": (C.c_int, [C.POINTER(NbSmplModel), _P, _I32, C.c_int, _P, _P, _P, _P]),
     "nb_smpl_voxelize": (C.c_int, [_P, _I32, _I32, _P, _P, _I64, C.c_double * 3, C.c_int, _P, _P, _P, _P, _P, _P]),
+    "nb_smpl_silhouette_scratch_size": (_I64, [_I32, _I32, _I32, _I32]),
+    "nb_smpl_silhouette": (C.c_int, [_P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _P, _I64, _P, _P]),
 }
 
 _lib = None

@@ -141,6 +141,22 @@ __device__ __forceinline__ bool cull_inside(const CullDev &c, const SceneDev &sc
     return inside;
 }
 
+// One view's projection of cull_inside, operation for operation, for code that needs the numbers and not the mask lookup
+// (nb_silhouette.hip): t = RT . (p, 1), q = K . t; the pixel is q.xy / q.z under __fdiv_rn.  These eight lines DUPLICATE the loop
+// body of cull_inside, which is left as it is; a change to either must be made to both.  What holds them together is
+// tests/test_gpu_silhouette.py: every device mask equals silhouette_ref.snapped_mask, the same operations in numpy float32.
+__device__ __forceinline__ void cull_project(cfloat_ptr RT, const float p[3], float t[3], float q[3]) {
+    cfloat_ptr K = RT + 12;
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+        t[i] = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(p[0], RT[i * 4]), __fmul_rn(p[1], RT[i * 4 + 1])),
+                                   __fmul_rn(p[2], RT[i * 4 + 2])), RT[i * 4 + 3]);
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+        q[i] = __fadd_rn(__fadd_rn(__fmul_rn(t[0], K[i * 3]), __fmul_rn(t[1], K[i * 3 + 1])),
+                         __fmul_rn(t[2], K[i * 3 + 2]));
+}
+
 struct MarchArgs {
     SceneDev sc;
     CullDev cull;

@@ -1,0 +1,218 @@
+// nb_silhouette.hip — nb_smpl_silhouette: the posed body's triangles rasterised into a handful of cull cameras, conservatively and
+// exactly, as a stand-in for the training-view masks a pose that was never photographed does not have.
+//
+// Stands where (zju3dv/neuralbody):
+//   lib/datasets/light_stage/multi_view_perform_dataset.py:105-127  get_mask: the CIHP masks of real images, read from disk
+//   lib/networks/renderer/if_clight_renderer_mmsk.py:12-45          the consumer: round -> clamp lookup of a sample's pixel
+// Vertices go through the cull's projection (cull_project, beside cull_inside in nb_march_common.h) and are snapped to 1/256 pixel; everything
+// behind the snap is integer arithmetic (edge functions in int64, |coordinate| <= 2^23, every product < 2^48), so the mask is a
+// function of the inputs alone.  The output is a union of 1 bytes: racing identical stores, no ordering, the same bits every time.
+// The one atomic (a wave's slice of the large-triangle list) orders list entries, which no output bit depends on.
+#include "nb_march_common.h"
+
+namespace {
+
+constexpr int SUB = 256, HALF = SUB / 2;      // sub-pixel units per pixel; a pixel is the closed square centre -+ HALF
+static_assert(SUB == 1 << 8, "tri_setup divides by SUB with >> 8");
+constexpr float MIN_DEPTH = 0.01f;            // metres in front of the camera
+constexpr float MAX_PIXEL = 32768.0f;         // |u|, |w| beyond it: the view does not cull
+constexpr int SMALL_BOX = 16;                 // clipped bounding boxes up to SMALL_BOX x SMALL_BOX are walked by one thread
+constexpr int LARGE_BLOCKS = 512;             // the large-triangle launch: a fixed grid striding over the device-side count
+constexpr int HDR_COUNT = 0, HDR_FLAGS = 4;   // scratch header, int32: large-triangle count | pad | flag of every (frame, view)
+
+struct Scratch {
+    int *hdr;     // [HDR_FLAGS + F * nv]
+    int2 *snap;   // [F * nv, V] snapped pixel coordinates
+    int *large;   // [F * nv * Nf] (frame, view, triangle) ids of the triangles one thread does not walk
+    long long hdr_bytes, total_bytes;
+};
+
+// 0 total_bytes: dimensions the entry refuses
+Scratch carve(void *base, long long F, long long V, long long Nf, long long nv) {
+    Scratch s = {};
+    if (F < 1 || V < 1 || Nf < 1 || nv < 1 || nv > NB_MAX_CULL_VIEWS || F > 65535) return s;
+    const long long fv = F * nv;
+    // a whole workgroup past the last id must still fit an int: the grids index vertices and triangles with int
+    if (fv * V > 2147483647ll - 256 || fv * Nf > 2147483647ll - 256) return s;
+    s.hdr_bytes = nb_align256(4 * (HDR_FLAGS + fv));
+    const long long snap_bytes = nb_align256(8 * fv * V), large_bytes = nb_align256(4 * fv * Nf);
+    char *p = (char *)base;
+    s.hdr = (int *)p;
+    s.snap = (int2 *)(p + s.hdr_bytes);
+    s.large = (int *)(p + s.hdr_bytes + snap_bytes);
+    s.total_bytes = s.hdr_bytes + snap_bytes + large_bytes;
+    return s;
+}
+
+// One workgroup = 256 vertices of one (frame, view): the camera is wave-uniform.
+__global__ __launch_bounds__(256) void sil_project_kernel(const float *__restrict__ verts, const float *__restrict__ cam, int V, int nv,
+                                                          int chunks, int2 *__restrict__ snap, int *__restrict__ flags) {
+    const int fv = blockIdx.x / chunks, v = (blockIdx.x % chunks) * 256 + threadIdx.x;
+    if (v >= V) return;
+    const int f = fv / nv, view = fv % nv;
+    const float *__restrict__ pv = verts + ((size_t)f * V + v) * 3;
+    const float p[3] = {pv[0], pv[1], pv[2]};
+    float t[3], q[3];
+    nbm::cull_project((nbm::cfloat_ptr)(cam + view * 21), p, t, q);
+    const float u = __fdiv_rn(q[0], q[2]), w = __fdiv_rn(q[1], q[2]);
+    // written so that a NaN anywhere lands on the safe side
+    const bool ok = t[2] >= MIN_DEPTH && fabsf(u) <= MAX_PIXEL && fabsf(w) <= MAX_PIXEL;
+    int2 s = {0, 0};
+    if (ok) {
+        s.x = (int)rintf((float)SUB * u);  // |256 u| <= 2^23: exact in fp32, half to even
+        s.y = (int)rintf((float)SUB * w);
+    } else {
+        flags[fv] = 1;  // racing stores of the same value
+    }
+    snap[(size_t)fv * V + v] = s;
+}
+
+// out = the flag of its (frame, view): 0 where the rasteriser will draw, 1 where the view does not cull.  16 bytes per thread.
+__global__ __launch_bounds__(256) void sil_fill_kernel(const int *__restrict__ flags, long long HW, long long n, int aligned,
+                                                       unsigned char *__restrict__ out) {
+    const long long b = ((long long)blockIdx.x * 256 + threadIdx.x) * 16;
+    if (b >= n) return;
+    const long long e = min(b + 16, n);
+    const long long i0 = b / HW, i1 = (e - 1) / HW;
+    if (aligned && e - b == 16 && i0 == i1) {
+        const unsigned w = flags[i0] ? 0x01010101u : 0u;
+        *reinterpret_cast<uint4 *>(out + b) = make_uint4(w, w, w, w);
+        return;
+    }
+    for (long long k = b; k < e; ++k) out[k] = flags[k / HW] ? 1 : 0;
+}
+
+// A triangle of one (frame, view), set up from the snapped vertices: oriented to positive area, its bounding box in pixels
+// clipped to the image, the three edge functions.  Pixel (x, y) is covered iff for every edge
+//   E_i(256 x, 256 y) + 128 (|dx_i| + |dy_i|) >= 0,
+// the largest value E_i takes on the closed square: the separating-axis test of square against triangle (the box is the other
+// two axes).
+struct Tri {
+    int x0, x1, y0, y1;          // clipped pixel box, empty when x0 > x1 or y0 > y1
+    long long dx[3], dy[3], c[3];  // E_i(X, Y) = dx_i Y - dy_i X + c_i, the slack already in c_i
+    __device__ __forceinline__ bool covers(int x, int y) const {
+        const long long X = (long long)x * SUB, Y = (long long)y * SUB;
+        return (dx[0] * Y - dy[0] * X + c[0] >= 0) & (dx[1] * Y - dy[1] * X + c[1] >= 0) & (dx[2] * Y - dy[2] * X + c[2] >= 0);
+    }
+};
+
+// false: nothing to draw (a flagged view, an index outside the vertices, zero area, a box off the image)
+__device__ __forceinline__ bool tri_setup(int g, int Nf, int V, int H, int W, const int *__restrict__ faces,
+                                          const int2 *__restrict__ snap, const int *__restrict__ flags, Tri &T, int &fv) {
+    fv = g / Nf;
+    const int tri = g - fv * Nf;
+    if (flags[fv]) return false;
+    const int ia = faces[3 * (size_t)tri], ib = faces[3 * (size_t)tri + 1], ic = faces[3 * (size_t)tri + 2];
+    if ((unsigned)ia >= (unsigned)V || (unsigned)ib >= (unsigned)V || (unsigned)ic >= (unsigned)V) return false;
+    const int2 *__restrict__ sv = snap + (size_t)fv * V;
+    const int2 a = sv[ia];
+    int2 b = sv[ib], c = sv[ic];
+    const long long area = (long long)(b.x - a.x) * (c.y - a.y) - (long long)(b.y - a.y) * (c.x - a.x);
+    if (area == 0) return false;
+    if (area < 0) {
+        const int2 s = b;
+        b = c;
+        c = s;
+    }
+    const int minx = min(a.x, min(b.x, c.x)), maxx = max(a.x, max(b.x, c.x));
+    const int miny = min(a.y, min(b.y, c.y)), maxy = max(a.y, max(b.y, c.y));
+    // the squares 256 x -+ 128 that meet [minx, maxx]: ceil((minx - 128) / 256) .. floor((maxx + 128) / 256)
+    T.x0 = max((minx + HALF - 1) >> 8, 0), T.x1 = min((maxx + HALF) >> 8, W - 1);
+    T.y0 = max((miny + HALF - 1) >> 8, 0), T.y1 = min((maxy + HALF) >> 8, H - 1);
+    if (T.x0 > T.x1 || T.y0 > T.y1) return false;
+    const int2 P[3] = {a, b, c}, Q[3] = {b, c, a};
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        T.dx[i] = (long long)Q[i].x - P[i].x;
+        T.dy[i] = (long long)Q[i].y - P[i].y;
+        const long long adx = T.dx[i] < 0 ? -T.dx[i] : T.dx[i], ady = T.dy[i] < 0 ? -T.dy[i] : T.dy[i];
+        T.c[i] = T.dy[i] * P[i].x - T.dx[i] * P[i].y + HALF * (adx + ady);
+    }
+    return true;
+}
+
+// One thread per (frame, view, triangle): small boxes are walked here, the others listed for sil_large_kernel.
+__global__ __launch_bounds__(256) void sil_small_kernel(const int *__restrict__ faces, const int2 *__restrict__ snap,
+                                                        const int *__restrict__ flags, int n, int Nf, int V, int H, int W,
+                                                        int *__restrict__ count, int *__restrict__ large,
+                                                        unsigned char *__restrict__ out) {
+    const int g = blockIdx.x * 256 + threadIdx.x;
+    Tri T;
+    int fv = 0;
+    const bool draw = g < n && tri_setup(g, Nf, V, H, W, faces, snap, flags, T, fv);
+    const bool big = draw && (T.x1 - T.x0 >= SMALL_BOX || T.y1 - T.y0 >= SMALL_BOX);
+    // the wave's large triangles take consecutive list places: one atomic per wave that has any
+    const unsigned long long m = __ballot(big);
+    if (m) {
+        const int lane = threadIdx.x & 63, leader = __ffsll((long long)m) - 1;
+        int base = 0;
+        if (lane == leader) base = atomicAdd(count, __popcll(m));
+        base = __shfl(base, leader, 64);
+        if (big) large[base + __popcll(m & ((1ull << lane) - 1ull))] = g;  // < n places in all: every g is listed at most once
+    }
+    if (!draw || big) return;
+    unsigned char *__restrict__ img = out + (size_t)fv * H * W;
+    for (int y = T.y0; y <= T.y1; ++y)
+        for (int x = T.x0; x <= T.x1; ++x)
+            if (T.covers(x, y)) img[(size_t)y * W + x] = 1;
+}
+
+// One workgroup per listed triangle, its threads striding over the clipped box.
+__global__ __launch_bounds__(256) void sil_large_kernel(const int *__restrict__ faces, const int2 *__restrict__ snap,
+                                                        const int *__restrict__ flags, int n, int Nf, int V, int H, int W,
+                                                        const int *__restrict__ count, const int *__restrict__ large,
+                                                        unsigned char *__restrict__ out) {
+    const int listed = min(*count, n);
+    for (int i = blockIdx.x; i < listed; i += gridDim.x) {
+        const int g = large[i];
+        if ((unsigned)g >= (unsigned)n) continue;
+        Tri T;
+        int fv;
+        if (!tri_setup(g, Nf, V, H, W, faces, snap, flags, T, fv)) continue;
+        unsigned char *__restrict__ img = out + (size_t)fv * H * W;
+        const int bw = T.x1 - T.x0 + 1;
+        const long long px = (long long)bw * (T.y1 - T.y0 + 1);
+        for (long long p = threadIdx.x; p < px; p += 256) {
+            const int y = T.y0 + (int)(p / bw), x = T.x0 + (int)(p % bw);
+            if (T.covers(x, y)) img[(size_t)y * W + x] = 1;
+        }
+    }
+}
+
+}  // namespace
+
+extern "C" int64_t nb_smpl_silhouette_scratch_size(int32_t F, int32_t V, int32_t Nf, int32_t nv) {
+    return carve(nullptr, F, V, Nf, nv).total_bytes;
+}
+
+extern "C" int nb_smpl_silhouette(const float *verts, const int32_t *faces, const float *cam, int32_t F, int32_t V, int32_t Nf,
+                                  int32_t nv, int32_t H, int32_t W, void *scratch, int64_t scratch_bytes, uint8_t *out,
+                                  void *stream) {
+    NB_REQUIRE(verts && faces && cam && scratch && out, "nb_smpl_silhouette: NULL pointer");
+    const Scratch s = carve(scratch, F, V, Nf, nv);
+    NB_REQUIRE(s.total_bytes > 0,
+               "nb_smpl_silhouette: F = %d (1..65535), V = %d, Nf = %d (>= 1), nv = %d (1..%d), F nv V and F nv Nf below 2^31 - 256", F, V,
+               Nf, nv, NB_MAX_CULL_VIEWS);
+    NB_REQUIRE(H >= 1 && W >= 1 && H <= 32768 && W <= 32768, "nb_smpl_silhouette: H = %d, W = %d (1..32768)", H, W);
+    NB_REQUIRE(scratch_bytes >= s.total_bytes, "nb_smpl_silhouette: scratch holds %lld bytes, %lld needed", (long long)scratch_bytes,
+               s.total_bytes);
+    NB_REQUIRE(((uintptr_t)scratch & 15) == 0, "nb_smpl_silhouette: scratch must be 16-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    const int fv = F * nv, chunks = nb_ceil_div(V, 256), n_tri = fv * Nf;
+    const long long HW = (long long)H * W, n_px = HW * fv;
+    NB_REQUIRE((n_px + 16 * 256 - 1) / (16 * 256) <= 2147483647ll, "nb_smpl_silhouette: %lld output bytes are too many", n_px);
+    int *flags = s.hdr + HDR_FLAGS, *count = s.hdr + HDR_COUNT;
+    NB_HIP(hipMemsetAsync(s.hdr, 0, (size_t)s.hdr_bytes, st));  // the count and every flag
+    hipLaunchKernelGGL(sil_project_kernel, dim3(fv * chunks), dim3(256), 0, st, verts, cam, V, nv, chunks, s.snap, flags);
+    NB_CHECK_LAUNCH("nb_smpl_silhouette (project)");
+    hipLaunchKernelGGL(sil_fill_kernel, dim3(nb_ceil_div(n_px, 16 * 256)), dim3(256), 0, st, flags, HW, n_px,
+                       ((uintptr_t)out & 15) == 0 ? 1 : 0, out);
+    NB_CHECK_LAUNCH("nb_smpl_silhouette (fill)");
+    hipLaunchKernelGGL(sil_small_kernel, dim3(nb_ceil_div(n_tri, 256)), dim3(256), 0, st, faces, s.snap, flags, n_tri, Nf, V, H, W, count,
+                       s.large, out);
+    NB_CHECK_LAUNCH("nb_smpl_silhouette (triangles)");
+    hipLaunchKernelGGL(sil_large_kernel, dim3(LARGE_BLOCKS), dim3(256), 0, st, faces, s.snap, flags, n_tri, Nf, V, H, W, count, s.large,
+                       out);
+    NB_CHECK_LAUNCH("nb_smpl_silhouette (large triangles)");
+    return NB_OK;
+}

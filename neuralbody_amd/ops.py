@@ -1170,3 +1170,51 @@ def smpl_voxelize(verts, Rh, Th, voxel_size, pad="zju"):
                                           ptr(out["coord"]), ptr(out["out_sh"]), ptr(out["bounds"]), ptr(out["R"]),
                                           ptr(out["summary"]), _stream()), "nb_smpl_voxelize")
     return out
+
+
+# ------------------------------------------------------------------------------------------- cull masks of a posed body
+def smpl_silhouette_scratch(F, V, Nf, nv, device):
+    """Scratch of smpl_silhouette for F frames of V vertices and Nf triangles in nv views."""
+    n = int(_lib.lib().nb_smpl_silhouette_scratch_size(int(F), int(V), int(Nf), int(nv)))
+    if n <= 0:
+        raise ValueError("no silhouettes for F = %d, V = %d, Nf = %d, nv = %d (F 1..65535, nv 1..64, F nv V and F nv Nf < 2^31)" % (
+            F, V, Nf, nv))
+    return torch.empty(n, dtype=torch.uint8, device=device)
+
+
+def smpl_silhouette(verts, faces, RT, K, H, W, out=None, scratch=None):
+    """nb_smpl_silhouette: verts device fp32 [F,V,3] (world), faces device int32 [Nf,3] (indices 0..V-1, validated where the list
+    is made: SmplModel), RT [nv,3,4], K [nv,3,3] device tensors (the cull cameras, as make_cull takes them), H, W the mask size
+    -> device uint8 [F,nv,H,W], 1 where the body's triangles meet the pixel; nothing is read back."""
+    _req(verts, torch.float32, (None, None, 3), "verts")
+    _req(faces, torch.int32, (None, 3), "faces")
+    F, V, Nf, dev = int(verts.shape[0]), int(verts.shape[1]), int(faces.shape[0]), verts.device
+    H, W = int(H), int(W)
+    if F < 1 or V < 1 or Nf < 1:
+        raise ValueError("verts %s or faces %s is empty" % (tuple(verts.shape), tuple(faces.shape)))
+    if not 1 <= H <= 32768 or not 1 <= W <= 32768:
+        raise ValueError("H = %d, W = %d (1..32768)" % (H, W))
+    for name, t in (("RT", RT), ("K", K)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError("%s must be a torch.Tensor" % name)
+        if not t.is_cuda:
+            raise NbError("%s must live on a HIP device (got %s); the HIP path has no CPU fallback" % (name, t.device))
+    nv = int(K.shape[0])
+    if not 1 <= nv <= 64:
+        raise ValueError("1..64 mask views supported, got %d" % nv)
+    if tuple(RT.shape) != (nv, 3, 4) or tuple(K.shape) != (nv, 3, 3):
+        raise ValueError("RT %s, K %s: expected [%d,3,4] and [%d,3,3]" % (tuple(RT.shape), tuple(K.shape), nv, nv))
+    if faces.device != dev or RT.device != dev or K.device != dev:
+        raise ValueError("verts, faces, RT and K live on different devices")
+    cam = torch.cat([RT.detach().reshape(nv, 12).float(), K.detach().reshape(nv, 9).float()], 1).contiguous()
+    _req(cam, torch.float32, (nv, 21), "cam")
+    if scratch is None:
+        scratch = smpl_silhouette_scratch(F, V, Nf, nv, dev)
+    _req(scratch, torch.uint8, (None,), "scratch")
+    if out is None:
+        out = torch.empty((F, nv, H, W), dtype=torch.uint8, device=dev)
+    _req(out, torch.uint8, (F, nv, H, W), "out")
+    with torch.cuda.device(dev):
+        check(_lib.lib().nb_smpl_silhouette(ptr(verts), ptr(faces), ptr(cam), F, V, Nf, nv, H, W, ptr(scratch), int(scratch.numel()),
+                                            ptr(out), _stream()), "nb_smpl_silhouette")
+    return out

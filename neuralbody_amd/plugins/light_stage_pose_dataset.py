@@ -9,6 +9,9 @@ and, in the YAML (the reference's command line refuses keys its config.py does n
 
     smpl_model_path: data/zju_mocap/smplx/smpl/SMPL_NEUTRAL.pkl
     smpl_new_params: true      # default: 'new' in cfg.params, the rule of zju_smpl/extract_vertices.py:14-16
+    cull_views: [0, 6, 12, 18] # default []: no culling.  Cameras of the annotations whose silhouettes of the posed body are
+                               # rasterised on the device; the items then hold msks / Ks / RT for the _mmsk renderer
+    cull_margin: 0.05          # metres the silhouettes are dilated by (clothing, hair); the default is the box padding
 """
 import os
 import sys
@@ -32,6 +35,8 @@ class _LiveCfg:
     big_box = property(lambda self: bool(cfg.big_box))
     # not a reference key: YAML only
     smpl_new_params = property(lambda self: bool(getattr(cfg, "smpl_new_params", "new" in str(getattr(cfg, "params", "params")))))
+    cull_views = property(lambda self: tuple(int(v) for v in getattr(cfg, "cull_views", ())))
+    cull_margin = property(lambda self: float(getattr(cfg, "cull_margin", 0.05)))
 
 
 def disk_source(data_root, human, ann_file):

@@ -8,7 +8,13 @@ one vertices/{i}.npy per frame) and then per item on the host (prepare_input of 
 
 A frame is the dict NovelViewRenderer.view_batch documents, so `PoseDriver.views` feeds NovelViewRenderer.render_views as a
 turntable's views do, and a frame change uploads 88 floats instead of the frame's coordinates from pageable memory.
+
+With `cull_cameras` a frame also carries the keys RendererMmsk culls by (msks, Ks, RT): the posed triangles rasterised into those
+cameras (nb_smpl_silhouette, enqueued with the launches above) and dilated by a clothing margin (nb_mask_dilate, one launch per
+frame once the summary has told the host how near the body is), in place of the masks of photographs
+(multi_view_perform_dataset.py:105-127) a pose that was never photographed does not have.
 """
+import math
 import os
 import pickle
 
@@ -30,22 +36,47 @@ def _dense(a, dtype):
 class SmplModel:
     """The SMPL model's arrays on a device, laid out for nb_smpl_pose (include/nb_hip.h: nb_smpl_model), uploaded once."""
 
-    def __init__(self, host, parents, device="cuda:0"):
-        """`host`: the float32 arrays of `host_arrays`; use from_arrays / from_pkl."""
+    def __init__(self, host, parents, device="cuda:0", faces=None):
+        """`host`: the float32 arrays of `host_arrays`, `faces`: the int32 [Nf,3] of `host_faces` or None; use from_arrays /
+        from_pkl."""
         self.device = torch.device(device)
         self.parents = [int(p) for p in parents]
         self.n_verts = int(host["v_template"].shape[0])
         self.host = host
+        self.faces = faces
         self._dev = None  # made on first use: constructing the model touches no device
 
     @staticmethod
+    def host_faces(arrays, n_verts):
+        """The triangle list of the pickle's arrays (`f`, or `faces`) -> a contiguous int32 [Nf,3], or None when they hold none.
+        ValueError for a shape other than [Nf,3] with Nf >= 1, or an index outside 0 .. n_verts - 1: the rasteriser trusts it."""
+        key = "f" if "f" in arrays else "faces" if "faces" in arrays else None
+        if key is None or arrays[key] is None:
+            return None
+        f = np.asarray(arrays[key])
+        if f.ndim != 2 or f.shape[1] != 3 or f.shape[0] < 1 or f.dtype.kind not in "iu":
+            raise ValueError("the triangle list %r must be integers [Nf,3] with Nf >= 1, got %s %s" % (key, f.dtype, f.shape))
+        f = f.astype(np.int64)
+        if int(f.min()) < 0 or int(f.max()) >= n_verts:
+            raise ValueError("the triangle list %r indexes vertices %d .. %d; the model has 0 .. %d" % (key, int(f.min()), int(f.max()),
+                                                                                                   n_verts - 1))
+        return np.ascontiguousarray(f, dtype=np.int32)
+
+    @staticmethod
     def host_arrays(arrays):
-        """The pickle's arrays -> (dict of float32 arrays in the kernels' layout, parents).  ValueError for what cannot be skinned
-        here: a joint count other than 24, a pose basis other than 207, shapes that do not fit one another."""
+        """The pickle's arrays -> (dict of float32 arrays in the kernels' layout, parents); see _host_arrays."""
+        return SmplModel._host_arrays(arrays)[:2]
+
+    @staticmethod
+    def _host_arrays(arrays):
+        """The pickle's arrays -> (dict of float32 arrays in the kernels' layout, parents, faces int32 [Nf,3] or None).  ValueError for what cannot be skinned
+        here: a joint count other than 24, a pose basis other than 207, shapes that do not fit one another, a triangle list
+        (`host_faces`; from_arrays keeps it beside these arrays) that does not index the vertices."""
         v_template = _dense(arrays["v_template"], np.float32)
         if v_template.ndim != 2 or v_template.shape[1] != 3 or v_template.shape[0] < 1:
             raise ValueError("v_template must be [V,3] with V >= 1, got %s" % (v_template.shape,))
         V = v_template.shape[0]
+        faces = SmplModel.host_faces(arrays, V)
         weights = _dense(arrays["weights"], np.float32)
         J_regressor = _dense(arrays["J_regressor"], np.float64)
         if "parents" in arrays:
@@ -82,14 +113,14 @@ class SmplModel:
         host = {"v_template": v_template, "shapedirs": np.ascontiguousarray(shapedirs.reshape(3 * V, N_BETAS).T),
                 "posedirs": np.ascontiguousarray(posedirs), "weights": np.ascontiguousarray(weights.T),
                 "j_template": j_template.astype(np.float32), "j_shapedirs": j_shapedirs.astype(np.float32)}
-        return {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in host.items()}, parents
+        return {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in host.items()}, parents, faces
 
     @classmethod
     def from_arrays(cls, arrays, device="cuda:0"):
         """`arrays`: v_template [V,3], shapedirs [V,3,10], posedirs [V,3,207] or [207,3V], J_regressor [24,V] (dense, or anything
-        with .todense()), weights [V,24], and kintree_table [2,24] or parents [24]."""
-        host, parents = cls.host_arrays(arrays)
-        return cls(host, parents, device)
+        with .todense()), weights [V,24], kintree_table [2,24] or parents [24], and optionally the triangles f (or faces) [Nf,3]."""
+        host, parents, faces = cls._host_arrays(arrays)
+        return cls(host, parents, device, faces)
 
     @classmethod
     def from_pkl(cls, path, device="cuda:0"):
@@ -104,8 +135,16 @@ class SmplModel:
             if self.device.type != "cuda":
                 raise ops.NbError("the SMPL model must live on a HIP device (got %s); the HIP path has no CPU fallback" % (self.device,))
             tensors = {k: torch.from_numpy(v).to(self.device) for k, v in self.host.items()}
+            if self.faces is not None:
+                tensors["faces"] = torch.from_numpy(self.faces).to(self.device)
             self._dev = ops.make_smpl_model(tensors, self.parents) + (tensors,)
         return self._dev[0], self._dev[2]
+
+    def faces_device(self):
+        """The triangle list on the device, int32 [Nf,3], uploaded with the model."""
+        if self.faces is None:
+            raise ops.NbError("the SMPL model has no triangle list (no 'f' or 'faces' among its arrays): silhouettes need one")
+        return self.native()[1]["faces"]
 
 
 def pack_params(poses, shapes, Rh, Th, pin=False):
@@ -124,6 +163,46 @@ def pack_params(poses, shapes, Rh, Th, pin=False):
     return out
 
 
+def cull_camera_arrays(cull_cameras):
+    """cull_cameras = (Ks [nv,3,3], RTs [nv,3,4] or [nv,4,4], H, W) -> (Ks, RTs [nv,3,4]) float64 on the host, H, W."""
+    if len(cull_cameras) != 4:
+        raise ValueError("cull_cameras must be (Ks [nv,3,3], RTs [nv,3,4] or [nv,4,4], H, W)")
+    as_np = lambda a: a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else a  # noqa: E731
+    Ks, RTs = np.asarray(as_np(cull_cameras[0]), np.float64), np.asarray(as_np(cull_cameras[1]), np.float64)
+    H, W = int(cull_cameras[2]), int(cull_cameras[3])
+    nv = Ks.shape[0] if Ks.ndim == 3 else 0
+    if not 1 <= nv <= 64 or Ks.shape != (nv, 3, 3) or RTs.shape not in ((nv, 3, 4), (nv, 4, 4)):
+        raise ValueError("cull_cameras: Ks %s, RTs %s (1..64 views, [nv,3,3] and [nv,3,4] or [nv,4,4])" % (Ks.shape, RTs.shape))
+    if H < 1 or W < 1:
+        raise ValueError("cull_cameras: H = %d, W = %d" % (H, W))
+    return Ks, np.ascontiguousarray(RTs[:, :3]), H, W
+
+
+def cull_border(can_bounds, Ks, RTs, cull_margin=0.05):
+    """The dilation that stands for `cull_margin` metres around the body, in pixels of the cull views: z_near = the smallest
+    camera depth of the eight corners of `can_bounds` [2,3] over the views, px = ceil(margin * max(fx, fy) / (z_near - margin)) + 1
+    (the + 1: the cull's round-to-nearest and its fp32 projection), border = 2 px + 1 -> border, odd, for nb_mask_dilate.
+    ValueError when the box comes within the margin of a camera, or the border passes 255."""
+    Ks, RTs = np.asarray(Ks, np.float64), np.asarray(RTs, np.float64)[:, :3]
+    cb, margin = np.asarray(can_bounds, np.float64).reshape(2, 3), float(cull_margin)
+    if not 0.0 <= margin < math.inf:
+        raise ValueError("cull_margin = %r m must be a finite length >= 0" % (cull_margin,))
+    corners = np.array([[cb[i, 0], cb[j, 1], cb[k, 2]] for i in (0, 1) for j in (0, 1) for k in (0, 1)])
+    depth = np.einsum("vk,ck->vc", RTs[:, 2, :3], corners) + RTs[:, 2, 3:4]  # [nv,8]
+    view = int(np.argmin(depth.min(axis=1)))
+    z_near = float(depth.min())
+    if not z_near > margin:
+        raise ValueError("cull_margin = %g m: the body's box comes within %.4f m of cull camera %d; no finite dilation covers the "
+                         "margin" % (margin, z_near, view))
+    focal = float(max(Ks[:, 0, 0].max(), Ks[:, 1, 1].max()))
+    px = int(math.ceil(margin * focal / (z_near - margin))) + 1
+    border = 2 * px + 1
+    if border > 255:
+        raise ValueError("cull_margin = %g m is %d pixels at cull camera %d (z_near %.4f m, focal %.1f px): border %d > 255, the "
+                         "most nb_mask_dilate takes" % (margin, px, view, z_near, focal, border))
+    return border
+
+
 class PoseDriver:
     """Frames of a body from its SMPL parameters.  `voxel_size`: cfg.voxel_size (three Python floats, dhw); `pad`: 'zju'
     (z -+ 0.05, the light-stage datasets), 'big_box' (cfg.big_box) or 'snapshot' (y -+ 0.1, People-Snapshot)."""
@@ -139,19 +218,30 @@ class PoseDriver:
         if self.device != model.device:
             raise ValueError("the driver's device %s is not the model's %s" % (self.device, model.device))
 
-    def _upload(self, poses, shapes, Rh, Th, latent_index=None):
-        """One pinned buffer, one copy: the [F,88] parameter rows and, behind them, F int64 latent indices -> (params [F,88]
-        fp32, latent [F] int64 or None), views of the one device buffer."""
+    def _upload(self, poses, shapes, Rh, Th, latent_index=None, cull=None):
+        """One pinned buffer, one copy: the [F,88] parameter rows and, behind them, F int64 latent indices and the cull cameras
+        (`cull`: the (Ks, RTs, H, W) of cull_camera_arrays) -> (params [F,88] fp32, latent [F] int64 or None, (RT [nv,3,4],
+        K [nv,3,3]) fp32 or None), views of the one device buffer."""
         rows = pack_params(poses, shapes, Rh, Th)
         F = int(rows.shape[0])
         n_par = F * N_PARAMS * 4  # a multiple of 8: the int64 section is aligned
-        host = torch.empty(n_par + (8 * F if latent_index is not None else 0), dtype=torch.uint8, pin_memory=self.device.type == "cuda")
+        n_lat = 8 * F if latent_index is not None else 0
+        nv = 0 if cull is None else int(cull[0].shape[0])
+        host = torch.empty(n_par + n_lat + 4 * 21 * nv, dtype=torch.uint8, pin_memory=self.device.type == "cuda")
         host[:n_par].view(torch.float32).view(F, N_PARAMS).copy_(rows)
         if latent_index is not None:
             lat = np.broadcast_to(np.asarray(latent_index, np.int64).reshape(-1), (F,))
-            host[n_par:].view(torch.int64).copy_(torch.from_numpy(np.array(lat)))
+            host[n_par:n_par + n_lat].view(torch.int64).copy_(torch.from_numpy(np.array(lat)))
+        if nv:
+            cam = np.concatenate([cull[1].reshape(-1), cull[0].reshape(-1)]).astype(np.float32)  # RT [nv,12], then K [nv,9]
+            host[n_par + n_lat:].view(torch.float32).copy_(torch.from_numpy(cam))
         dev = host.to(self.device, non_blocking=True)
-        return dev[:n_par].view(torch.float32).view(F, N_PARAMS), (dev[n_par:].view(torch.int64) if latent_index is not None else None)
+        cams = None
+        if nv:
+            c = dev[n_par + n_lat:].view(torch.float32)
+            cams = (c[:12 * nv].view(nv, 3, 4), c[12 * nv:].view(nv, 3, 3))
+        return (dev[:n_par].view(torch.float32).view(F, N_PARAMS), (dev[n_par:n_par + n_lat].view(torch.int64) if n_lat else None),
+                cams)
 
     def _on_device(self):
         """The calls below enqueue on the current stream of the driver's device, whichever device is current for the caller."""
@@ -165,13 +255,30 @@ class PoseDriver:
             native, _ = self.model.native()
             return ops.smpl_pose(native, self._upload(poses, shapes, Rh, Th)[0], new_params)[0]
 
-    def frames(self, poses, shapes, Rh, Th, latent_index, new_params=False):
+    def silhouettes(self, verts, cull_cameras):
+        """verts: device fp32 [F,V,3] (`vertices`), cull_cameras = (Ks [nv,3,3], RTs [nv,3,4] or [nv,4,4], H, W) -> the raw masks,
+        device uint8 [F,nv,H,W]: 1 where a triangle of the posed body meets the pixel, before any dilation (nb_smpl_silhouette)."""
+        Ks, RTs, H, W = cull_camera_arrays(cull_cameras)
+        with self._on_device():
+            faces = self.model.faces_device()
+            cam = torch.from_numpy(np.concatenate([RTs.reshape(-1), Ks.reshape(-1)]).astype(np.float32))
+            cam = (cam.pin_memory() if self.device.type == "cuda" else cam).to(self.device, non_blocking=True)
+            nv = Ks.shape[0]
+            return ops.smpl_silhouette(verts, faces, cam[:12 * nv].view(nv, 3, 4), cam[12 * nv:].view(nv, 3, 3), H, W)
+
+    def frames(self, poses, shapes, Rh, Th, latent_index, new_params=False, cull_cameras=None, cull_margin=0.05):
         """-> [(frame, can_bounds)] * F.  `frame`: device tensors coord [1,V,3] i32, out_sh [1,3] i32, bounds [1,2,3], R [1,3,3],
         Th [1,1,3], latent_index [1] (views of the call's [F,...] tensors); `can_bounds`: float32 [2,3] on the host, what
-        nb_raygen needs of the frame.  One upload, three launches, one wait: for the event behind the summary's copy."""
+        nb_raygen needs of the frame.  One upload, three launches, one wait: for the event behind the summary's copy.
+        `cull_cameras` = (Ks [nv,3,3], RTs [nv,3,4] or [nv,4,4], H, W): every frame also holds msks [1,nv,H,W] uint8, Ks
+        [1,nv,3,3] and RT [1,nv,3,4], the keys RendererMmsk.make_cull reads — the body's silhouettes in those cameras
+        (`silhouettes`, enqueued behind the voxelisation, before the wait) dilated by `cull_margin` metres (`cull_border` of the
+        frame's can_bounds; one nb_mask_dilate per frame after the wait, nothing else waits)."""
+        cull = None if cull_cameras is None else cull_camera_arrays(cull_cameras)
         with self._on_device():
+            faces = None if cull is None else self.model.faces_device()  # refuses a model without triangles before any launch
             native, _ = self.model.native()
-            params, latent = self._upload(poses, shapes, Rh, Th, latent_index)
+            params, latent, cams = self._upload(poses, shapes, Rh, Th, latent_index, cull)
             F = int(params.shape[0])
             verts, _ = ops.smpl_pose(native, params, new_params)
             vox = ops.smpl_voxelize(verts, params[:, 82:85], params[:, 85:88], self.voxel_size, self.pad)
@@ -179,23 +286,32 @@ class PoseDriver:
             summary.copy_(vox["summary"], non_blocking=True)
             ev = torch.cuda.Event()
             ev.record()
+            raw = None if cull is None else ops.smpl_silhouette(verts, faces, cams[0], cams[1], cull[2], cull[3])
             ev.synchronize()  # the copy and what it depends on; nothing enqueued by anyone after this point
-        s = summary.numpy()
+            s = summary.numpy()
+            can_bounds = [s[f, :6].copy().view(np.float32).reshape(2, 3) for f in range(F)]
+            if cull is not None:
+                borders = [cull_border(cb, cull[0], cull[1], cull_margin) for cb in can_bounds]  # all checked before any launch
+                msks = torch.empty_like(raw)
+                for f in range(F):
+                    ops.mask_dilate(raw[f], borders[f], out=msks[f])
         out = []
         for f in range(F):
             frame = {"coord": vox["coord"][f:f + 1], "out_sh": vox["out_sh"][f:f + 1], "bounds": vox["bounds"][f:f + 1],
                      "R": vox["R"][f:f + 1], "Th": params[f:f + 1, None, 85:88], "latent_index": latent[f:f + 1]}
-            out.append((frame, s[f, :6].copy().view(np.float32).reshape(2, 3)))
+            if cull is not None:
+                frame.update(msks=msks[f:f + 1], Ks=cams[1][None], RT=cams[0][None])
+            out.append((frame, can_bounds[f]))
         return out
 
-    def views(self, cameras, poses, shapes, Rh, Th, latent_index, new_params=False):
+    def views(self, cameras, poses, shapes, Rh, Th, latent_index, new_params=False, cull_cameras=None, cull_margin=0.05):
         """Generator of (K, RT, can_bounds, frame) for NovelViewRenderer.render_views.  `cameras`: a list of (K, RT) pairs, one per
         frame, or a list of ONE pair that every frame is seen by.  All frames are made by one call of `frames` before the
-        first view is yielded."""
+        first view is yielded.  `cull_cameras`, `cull_margin`: those of `frames`; the frames then feed a RendererMmsk."""
         cameras = list(cameras)
         if any(len(c) != 2 for c in cameras):
             raise ValueError("cameras must be a list of (K, RT) pairs")
-        made = self.frames(poses, shapes, Rh, Th, latent_index, new_params)
+        made = self.frames(poses, shapes, Rh, Th, latent_index, new_params, cull_cameras, cull_margin)
         if len(cameras) not in (1, len(made)):
             raise ValueError("%d cameras for %d frames (one per frame, or one for all)" % (len(cameras), len(made)))
         for f, (frame, can_bounds) in enumerate(made):
@@ -205,24 +321,34 @@ class PoseDriver:
 
 # ------------------------------------------------------------------------------------------- dataset core
 class PoseDataConfig:
-    """The cfg keys the dataset core reads, plus the two of its own (`smpl_new_params`; the model comes in as an object)."""
+    """The cfg keys the dataset core reads, plus its own (`smpl_new_params`; `cull_views`, the camera indices of the annotations
+    whose silhouettes cull the items, empty = none; `cull_margin` in metres; the model comes in as an object)."""
 
     def __init__(self, begin_ith_frame=0, frame_interval=1, num_train_frame=1, voxel_size=(0.005, 0.005, 0.005), big_box=False,
-                 smpl_new_params=False):
+                 smpl_new_params=False, cull_views=(), cull_margin=0.05):
         self.begin_ith_frame, self.frame_interval, self.num_train_frame = int(begin_ith_frame), int(frame_interval), int(num_train_frame)
         self.voxel_size, self.big_box, self.smpl_new_params = tuple(voxel_size), bool(big_box), bool(smpl_new_params)
+        self.cull_views, self.cull_margin = tuple(int(v) for v in cull_views), float(cull_margin)
 
 
 class MemoryPoseSource:
     """Frames already in memory: `items[i]` = dict(poses, shapes, Rh, Th), seen by one camera K [3,3], R [3,3], T [3] (metres)
-    in an H x W image."""
+    in an H x W image.  `cull_cameras`: optionally the (Ks, RTs, H, W) of every camera cfg.cull_views may name."""
 
-    def __init__(self, items, K, R, T, H, W):
+    def __init__(self, items, K, R, T, H, W, cull_cameras=None):
         self.items, self.n_items = list(items), len(items)
         self.K, self.R, self.T, self.H, self.W = K, R, T, int(H), int(W)
+        self.cull = cull_cameras
 
     def load(self, i):
         return self.items[i]
+
+    def cull_cameras(self, views):
+        if self.cull is None:
+            raise ValueError("cull_views %s: this source was given no cull_cameras" % (list(views),))
+        Ks, RTs, H, W = cull_camera_arrays(self.cull)
+        views = [int(v) for v in views]
+        return Ks[views], RTs[views], H, W
 
 
 class LightStagePoseSource:
@@ -234,6 +360,7 @@ class LightStagePoseSource:
                  num_render_frame=-1, params="params"):
         self.data_root, self.human, self.params = data_root, human, params
         cams = np.load(ann_file, allow_pickle=True).item()["cams"]
+        self._cams, self._ratio = cams, ratio
         self.K = np.array(cams["K"][view], np.float64)
         self.K[:2] = self.K[:2] * ratio
         self.R = np.array(cams["R"][view], np.float64)
@@ -248,10 +375,23 @@ class LightStagePoseSource:
             i = i + 1
         return np.load(os.path.join(self.data_root, self.params, "{}.npy".format(i)), allow_pickle=True).item()
 
+    def cull_cameras(self, views):
+        """The cameras `views` of the annotations as render_utils.load_cam makes them (render_utils.py:37-48: K[:2] * ratio,
+        T / 1000) -> (Ks [nv,3,3], RTs [nv,3,4], H, W) at the reduced image size."""
+        Ks, RTs = [], []
+        for v in views:
+            K = np.array(self._cams["K"][int(v)], np.float64)
+            K[:2] = K[:2] * self._ratio
+            Ks.append(K)
+            RTs.append(np.concatenate([np.array(self._cams["R"][int(v)], np.float64),
+                                       np.array(self._cams["T"][int(v)], np.float64).reshape(3, 1) / 1000.0], axis=1))
+        return np.stack(Ks), np.stack(RTs), self.H, self.W
+
 
 class PoseFrameDataset(torch.utils.data.Dataset):
     """Item i = frame begin_ith_frame + i * frame_interval, made from its SMPL parameters and seen by the source's camera: the
-    batch dict Renderer.render consumes (before collation), all device tensors, with every pixel's ray from nb_raygen."""
+    batch dict Renderer.render consumes (before collation), all device tensors, with every pixel's ray from nb_raygen.  With
+    cfg.cull_views the item also holds msks [nv,H,W], Ks [nv,3,3], RT [nv,3,4]: what RendererMmsk culls by."""
 
     def __init__(self, source, model, cfg, device="cuda:0"):
         super().__init__()
@@ -270,11 +410,16 @@ class PoseFrameDataset(torch.utils.data.Dataset):
         cfg, src = self.cfg, self.source
         p = src.load(index)
         driver = PoseDriver(self.model, cfg.voxel_size, "big_box" if cfg.big_box else "zju", self.device)
-        (frame, can_bounds), = driver.frames(p["poses"], p["shapes"], p["Rh"], p["Th"], self.latent_index(index), cfg.smpl_new_params)
+        cull_views = tuple(getattr(cfg, "cull_views", ()))
+        cull = src.cull_cameras(cull_views) if cull_views else None
+        (frame, can_bounds), = driver.frames(p["poses"], p["shapes"], p["Rh"], p["Th"], self.latent_index(index), cfg.smpl_new_params,
+                                             cull, float(getattr(cfg, "cull_margin", 0.05)))
         ray_o, ray_d, near, far, mask, n_rays = ops.raygen(src.H, src.W, src.K, src.R, src.T, can_bounds, self.device)
         n = int(n_rays.item())
         ret = {"ray_o": ray_o[:n], "ray_d": ray_d[:n], "near": near[:n], "far": far[:n], "mask_at_box": mask.view(torch.bool),
                "coord": frame["coord"][0], "out_sh": frame["out_sh"][0], "bounds": frame["bounds"][0], "R": frame["R"][0],
                "Th": frame["Th"][0], "latent_index": frame["latent_index"][0],
                "frame_index": cfg.begin_ith_frame + index * cfg.frame_interval}
+        if cull is not None:
+            ret.update(msks=frame["msks"][0], Ks=frame["Ks"][0], RT=frame["RT"][0])
         return ret
