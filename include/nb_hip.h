@@ -399,6 +399,10 @@ int nb_enc_conv16(const uint16_t *in_split, int32_t in_rows_cap, const int32_t *
                   const int32_t *out_lin, const int32_t *n_out, int32_t n_out_max, const int32_t out_dhw[3],
                   int32_t stride, const uint16_t *wpacked, int32_t cin, int32_t cout, float *out_rows, double *stats,
                   int32_t flags, void *stream);
+/* Which forward kernel nb_enc_conv16 runs for a channel pair and a row CAPACITY (host only, launches nothing): 0 = offsets split over
+ * 8 waves, 1 = weight slab through LDS with every channel tile per wave, 2 = ... with two channel tiles per wave, 3 = per-wave
+ * operands with every channel tile per wave, 4 = ... with one channel tile per wave; -1: not a pair of nb_enc_conv16. */
+int nb_enc_conv16_variant(int32_t cin, int32_t cout, int32_t n_out_max);
 
 /* ---- encoder backward (training).  Shapes as in the forward calls above. ---- */
 

@@ -973,6 +973,14 @@ int nb_enc_conv16(const uint16_t *in_split, int32_t in_rows_cap, const int32_t *
     return (flags & NB_CONV_BF16) ? conv16_dispatch<true>(a) : conv16_dispatch<false>(a);
 }
 
+int nb_enc_conv16_variant(int32_t cin, int32_t cout, int32_t n_out_max) {
+#define X(CI, CO) \
+    if (CI >= 32 && CO >= 32 && ((cin == CI && cout == CO) || (cin == CO && cout == CI))) return (int)conv16_variant(cin, cout, n_out_max);
+    NB_FOR_CONV_SHAPES(X)
+#undef X
+    return -1;
+}
+
 int nb_enc_gather_codes(const float *codes, const int32_t *rows_vert, const int32_t *n_rows, int32_t n_rows_max,
                         int32_t c, float *rows, void *stream) {
     NB_REQUIRE(codes && rows_vert && n_rows && rows, "nb_enc_gather_codes: NULL pointer");

@@ -520,6 +520,16 @@ def enc_conv16(in_split, in_grid, in_dhw, out_lin, n_out, n_out_max, out_dhw, st
                      2 if bf16 else 0, pre=(int(in_split.shape[1]),))  # NB_CONV_BF16
 
 
+CONV16_VARIANTS = ("KS", "LDS_ALL_TILES", "LDS_TWO_TILES", "WAVE_ALL_TILES", "WAVE_ONE_TILE")
+
+
+def enc_conv16_variant(cin, cout, n_out_max):
+    """nb_enc_conv16_variant: the forward kernel enc_conv16 runs for this pair and row capacity, as a name of CONV16_VARIANTS (the
+    enum's order), or None for a pair it does not take.  Nothing is launched."""
+    v = int(_lib.lib().nb_enc_conv16_variant(int(cin), int(cout), int(n_out_max)))
+    return None if v < 0 else CONV16_VARIANTS[v]
+
+
 def enc_bn_relu_split(rows, n_rows, n_rows_max, stats, gamma, beta, running_mean, running_var, training, eps,
                       rows_lin=None, dense=None, momentum=-1.0, rows_out=None):
     """nb_enc_bn_relu_split -> (rows_split int16 [2, n_rows_max, C], batch_stats); rows_out (fp32, same shape as rows):
