@@ -649,6 +649,50 @@ int nb_smpl_silhouette(const float *verts, const int32_t *faces, const float *ca
                        int32_t n_faces, int32_t n_views, int32_t H, int32_t W, void *scratch, int64_t scratch_bytes, uint8_t *out,
                        void *stream);
 
+/* ---------------------------------------------------------------------------------
+ * Pictures of an extracted mesh on device — replaces the OpenGL renderer behind tools/render_mesh.py (tools/render/*: pyglet,
+ * PyOpenGL, GLSL) for the one thing the mesh workflow uses it for: orthographic, z-buffered, normal-shaded views.  No allocation,
+ * no synchronisation, everything on `stream`; every output is a function of the inputs alone (the same bits every call).
+ * "a (+) b" below is ONE fp32 operation rounded to nearest; no two are contracted into an FMA.
+ * nb_mesh_vertex_normals — compute_normal and normalize_v3 (tools/render_mesh.py:21-51).  verts dev [V,3] fp32, faces dev [T,3]
+ *   int32 (a face with an index outside 0..V-1 is skipped), acc dev [V,3] int32 scratch (zeroed here; a dirty buffer is fine),
+ *   normals dev [V,3] fp32 out.  Face normal: u = b (-) a, w = c (-) a, n = (u.y (*) w.z (-) u.z (*) w.y, ...), len =
+ *   max(sqrt((n.x (*) n.x (+) n.y (*) n.y) (+) n.z (*) n.z), 1e-8f), q = rint((n (/) len) (*) 2^20) as int32, added to the three
+ *   vertices' sums with integer atomics: the sums do not depend on arrival order.  |q| <= 2^20 + 1, so a vertex of valence up to
+ *   2047 cannot overflow (2047 (2^20 + 1) < 2^31).  A face whose q is not finite adds nothing.  Vertex normal: s = float(sum) (*)
+ *   2^-20, s (/) max(|s| as above, 1e-8f); a vertex used by no face gets (0, 0, 0).  0 <= V <= (2^31 - 257) / 3, 0 <= T <=
+ *   2^31 - 257, else NB_EINVAL.  A memset and two launches (a thread per face, a thread per vertex).
+ * nb_mesh_render — set_mesh / display / get_color of tools/render_mesh.py:146-167 for n_views cameras at once (color_render.py,
+ *   color.vs, color.fs; GL_LESS, no culling, no multisampling, white clear colour).  normals dev [V,3] fp32 (the call above);
+ *   cams dev [n_views, NB_MESH_CAM_FLOATS] fp32, per view: M 3x4 row-major, (x_px, y_px, d) = M . (v, 1) with row r evaluated as
+ *   ((M_r0 (*) v.x (+) M_r1 (*) v.y) (+) M_r2 (*) v.z) (+) M_r3 | N 3x3 row-major, the rotation of the normals, each row the same
+ *   three-term sum | 3 floats of padding (neuralbody_amd/mesh_render.py::turntable_cams composes both in float64).  Pixel (i, j)
+ *   (column, row) is sampled at (i + 1/2, j + 1/2); the smaller d is nearer.
+ *   Outputs: rgb dev [n_views,H,W,3] fp32; face_id dev [n_views,H,W] int32 or NULL; depth dev [n_views,H,W] fp32 or NULL.
+ *   Background is (1,1,1), -1, +inf; the whole of every output is written, so a dirty buffer is fine.
+ *   x_px, y_px are snapped to 1/256 pixel (rintf(256 x), half to even) and held as integers; the triangle is oriented to
+ *   positive area by exchanging its second and third vertex, attributes included.  Skipped: a face with an index outside
+ *   0..V-1, a non-finite x_px, y_px or d, |x_px| or |y_px| > 32768, zero snapped area.  Coverage is exact: with
+ *   E_i = the int64 edge function of the edge opposite vertex i at (256 i + 128, 256 j + 128), the pixel is covered iff
+ *   E_0, E_1, E_2 >= 0 (closed triangles, both windings).  l_i = float(E_i) (/) float(E_0 + E_1 + E_2); an attribute is
+ *   (a_0 (+) l_1 (*) (a_1 (-) a_0)) (+) l_2 (*) (a_2 (-) a_0): d, and each channel of the vertex colour 0.5 (*) (N . n) (+) 0.5.  A
+ *   sample whose d is not finite is not drawn.  The pixel keeps the sample with the smallest key = (bits of d, order-preserving,
+ *   -0 below +0) << 32 | triangle index: the smallest depth, a tie going to the lower triangle.
+ *   n_views >= 1, 1 <= H, W <= 32768, T >= 0 (T = 0: background), n_views H W and n_views T < 2^31 - 256, else NB_EINVAL.
+ *   scratch dev, 16-byte aligned: nb_mesh_render_scratch_size(n_views, H, W, T) bytes (0 for refused dimensions): a header, the
+ *   [n_views,H,W] uint64 keys, the list of large triangles.
+ *   Five stream operations: two memsets (the header; the keys to all ones), a thread per (view, triangle) that projects its three
+ *   vertices itself, walks a clipped box of at most 16 x 16 pixel centres and issues one 64-bit atomicMin per covered centre
+ *   (after a plain read of the key that may skip it), a fixed grid that gives each larger triangle a workgroup, and a thread per
+ *   pixel that decodes the winner, repeats its projection by the same function and interpolates the colour. */
+#define NB_MESH_CAM_FLOATS 24
+int nb_mesh_vertex_normals(const float *verts, const int32_t *faces, int32_t n_verts, int32_t n_faces, int32_t *acc,
+                           float *normals, void *stream);
+int64_t nb_mesh_render_scratch_size(int32_t n_views, int32_t H, int32_t W, int32_t n_faces);
+int nb_mesh_render(const float *verts, const float *normals, const int32_t *faces, int32_t n_verts, int32_t n_faces,
+                   const float *cams, int32_t n_views, int32_t H, int32_t W, float *rgb, int32_t *face_id, float *depth,
+                   void *scratch, int64_t scratch_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -135,6 +135,9 @@ SIGNATURES = {
     "nb_smpl_voxelize": (C.c_int, [_P, _I32, _I32, _P, _P, _I64, C.c_double * 3, C.c_int, _P, _P, _P, _P, _P, _P]),
     "nb_smpl_silhouette_scratch_size": (_I64, [_I32, _I32, _I32, _I32]),
     "nb_smpl_silhouette": (C.c_int, [_P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _P, _I64, _P, _P]),
+    "nb_mesh_vertex_normals": (C.c_int, [_P, _P, _I32, _I32, _P, _P, _P]),
+    "nb_mesh_render_scratch_size": (_I64, [_I32, _I32, _I32, _I32]),
+    "nb_mesh_render": (C.c_int, [_P, _P, _P, _I32, _I32, _P, _I32, _I32, _I32, _P, _P, _P, _P, _I64, _P]),
 }
 
 _lib = None
@@ -161,6 +164,10 @@ def lib():
     if not os.path.exists(LIB_PATH):
         raise NbError("libnb_hip.so is missing (%s). Build it with `python -m neuralbody_amd.build`; "
                       "there is no non-HIP fallback." % LIB_PATH)
+    # torch brings its own HIP runtime and loads it by path.  Loaded first, it is the one libnb_hip.so binds to; loaded after this
+    # library, the process holds two runtimes and the second one to initialise finds no device (build() then smoke() in one process)
+    import torch  # noqa: F401
+
     L = C.CDLL(LIB_PATH)
     for name, (res, args) in SIGNATURES.items():
         fn = getattr(L, name)  # AttributeError if the symbol is not exported

@@ -24,3 +24,51 @@ class TriMesh:
             f.write(self.vertices.astype("<f4").tobytes())
             f.write(faces.tobytes())
         return path
+
+    _SCALARS = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": "<i2", "int16": "<i2", "ushort": "<u2",
+                "uint16": "<u2", "int": "<i4", "int32": "<i4", "uint": "<u4", "uint32": "<u4", "float": "<f4", "float32": "<f4",
+                "double": "<f8", "float64": "<f8"}
+
+    @classmethod
+    def load_ply(cls, path):
+        """Reads what `export` and trimesh write: binary little-endian PLY, a vertex element with float or double x / y / z
+        (further scalar properties are skipped), then a face element of `list uchar int|uint` triangles.  Anything else is
+        refused with what was found."""
+        with open(str(path), "rb") as f:
+            data = f.read()
+        end = data.find(b"end_header\n")
+        if not data.startswith(b"ply") or end < 0:
+            raise ValueError("%s is not a PLY file (starts with %r)" % (path, data[:16]))
+        lines = [ln.split() for ln in data[:end].decode("ascii", "replace").splitlines()[1:]]
+        lines = [ln for ln in lines if ln and ln[0] not in ("comment", "obj_info")]
+        if not lines or lines[0][:2] != ["format", "binary_little_endian"]:
+            raise ValueError("%s: only binary_little_endian PLY is read, found %r" % (path, " ".join(lines[0]) if lines else ""))
+        elements = []
+        for ln in lines[1:]:
+            if ln[0] == "element" and len(ln) == 3:
+                elements.append((ln[1], int(ln[2]), []))
+            elif ln[0] == "property" and elements:
+                elements[-1][2].append(ln[1:])
+            else:
+                raise ValueError("%s: unexpected header line %r" % (path, " ".join(ln)))
+        if [e[0] for e in elements] != ["vertex", "face"]:
+            raise ValueError("%s: expected the elements vertex, face; found %s" % (path, [e[0] for e in elements]))
+        (_, nv, vprops), (_, nf, fprops) = elements
+        if any(len(p) != 2 or p[0] not in cls._SCALARS for p in vprops):
+            raise ValueError("%s: vertex properties must be scalars, found %s" % (path, [" ".join(p) for p in vprops]))
+        vdtype = np.dtype([(p[1], cls._SCALARS[p[0]]) for p in vprops])
+        if any(k not in vdtype.names or vdtype[k].kind != "f" or vdtype[k].itemsize < 4 for k in "xyz"):
+            raise ValueError("%s: x, y, z must be float or double vertex properties, found %s" % (path, [" ".join(p) for p in vprops]))
+        if len(fprops) != 1 or len(fprops[0]) != 4 or fprops[0][0] != "list" or cls._SCALARS.get(fprops[0][1]) != "u1" or \
+                cls._SCALARS.get(fprops[0][2]) not in ("<i4", "<u4"):
+            raise ValueError("%s: faces must be one `list uchar int|uint` property, found %s" % (path, [" ".join(p) for p in fprops]))
+        fdtype = np.dtype([("n", "u1"), ("v", cls._SCALARS[fprops[0][2]], (3,))])
+        body = end + len(b"end_header\n")
+        need = nv * vdtype.itemsize + nf * fdtype.itemsize
+        if len(data) - body < need:
+            raise ValueError("%s: %d bytes after the header, %d vertices and %d triangles need %d" % (path, len(data) - body, nv, nf, need))
+        verts = np.frombuffer(data, vdtype, nv, body)
+        faces = np.frombuffer(data, fdtype, nf, body + nv * vdtype.itemsize)
+        if nf and (faces["n"] != 3).any():
+            raise ValueError("%s: only triangles are read, found a face of %d vertices" % (path, int(faces["n"][faces["n"] != 3][0])))
+        return cls(np.stack([verts["x"], verts["y"], verts["z"]], 1), faces["v"])

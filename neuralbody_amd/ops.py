@@ -1228,3 +1228,77 @@ def smpl_silhouette(verts, faces, RT, K, H, W, out=None, scratch=None):
         check(_lib.lib().nb_smpl_silhouette(ptr(verts), ptr(faces), ptr(cam), F, V, Nf, nv, H, W, ptr(scratch), int(scratch.numel()),
                                             ptr(out), _stream()), "nb_smpl_silhouette")
     return out
+
+
+# ------------------------------------------------------------------------------------------- pictures of an extracted mesh
+MESH_CAM_FLOATS = 24  # NB_MESH_CAM_FLOATS: affine 3 x 4 | normal rotation 3 x 3 | 3 of padding
+
+
+def mesh_vertex_normals(vertices, triangles, out=None, scratch=None):
+    """nb_mesh_vertex_normals: vertices device fp32 [V,3], triangles device int32 [T,3] (a face with an index outside 0..V-1 is
+    skipped) -> device fp32 [V,3], compute_normal of tools/render_mesh.py:32-51 with order-independent sums; a vertex no face
+    uses gets (0,0,0).  scratch: the [V,3] int32 accumulator (allocated when None; a dirty one is fine).  Nothing is read back."""
+    _req(vertices, torch.float32, (None, 3), "vertices")
+    _req(triangles, torch.int32, (None, 3), "triangles")
+    V, T, dev = int(vertices.shape[0]), int(triangles.shape[0]), vertices.device
+    if triangles.device != dev:
+        raise ValueError("vertices and triangles live on different devices")
+    if scratch is None:
+        scratch = torch.empty((V, 3), dtype=torch.int32, device=dev)
+    _req(scratch, torch.int32, (V, 3), "scratch")
+    if out is None:
+        out = torch.empty((V, 3), dtype=torch.float32, device=dev)
+    _req(out, torch.float32, (V, 3), "out")
+    with torch.cuda.device(dev):
+        check(_lib.lib().nb_mesh_vertex_normals(ptr(vertices), ptr(triangles), V, T, ptr(scratch), ptr(out), _stream()),
+              "nb_mesh_vertex_normals")
+    return out
+
+
+def mesh_render_scratch(n_views, H, W, T, device):
+    """Scratch of mesh_render for n_views pictures of H x W pixels of T triangles."""
+    n = int(_lib.lib().nb_mesh_render_scratch_size(int(n_views), int(H), int(W), int(T)))
+    if n <= 0:
+        raise ValueError("no pictures for n_views = %d, H = %d, W = %d, T = %d (n_views >= 1, H, W 1..32768, n_views H W and "
+                         "n_views T < 2^31 - 256)" % (n_views, H, W, T))
+    return torch.empty(n, dtype=torch.uint8, device=device)
+
+
+def mesh_render(vertices, normals, triangles, cams, H, W, out=None, want_face_id=False, want_depth=False, scratch=None,
+                face_id=None, depth=None):
+    """nb_mesh_render: vertices, normals device fp32 [V,3], triangles device int32 [T,3], cams device fp32 [n,24] (per view the
+    3 x 4 affine to (x_px, y_px, depth) | the 3 x 3 rotation of the normals | 3 of padding: mesh_render.turntable_cams) ->
+    rgb device fp32 [n,H,W,3], white where nothing is drawn; with want_face_id and / or want_depth a tuple (rgb[, face_id int32
+    [n,H,W], -1 = background][, depth fp32 [n,H,W], +inf = background]); `face_id` / `depth` are buffers to fill for them (wanted
+    when given).  Nothing is read back."""
+    _req(vertices, torch.float32, (None, 3), "vertices")
+    V, dev = int(vertices.shape[0]), vertices.device
+    _req(normals, torch.float32, (V, 3), "normals")
+    _req(triangles, torch.int32, (None, 3), "triangles")
+    _req(cams, torch.float32, (None, MESH_CAM_FLOATS), "cams")
+    T, n, H, W = int(triangles.shape[0]), int(cams.shape[0]), int(H), int(W)
+    if normals.device != dev or triangles.device != dev or cams.device != dev:
+        raise ValueError("vertices, normals, triangles and cams live on different devices")
+    if n < 1:
+        raise ValueError("cams holds no view")
+    if V < 1:
+        T = 0  # nothing a face could index: every face would be skipped
+    if scratch is None:
+        scratch = mesh_render_scratch(n, H, W, T, dev)
+    _req(scratch, torch.uint8, (None,), "scratch")
+    if out is None:
+        out = torch.empty((n, H, W, 3), dtype=torch.float32, device=dev)
+    _req(out, torch.float32, (n, H, W, 3), "out")
+    if face_id is None and want_face_id:
+        face_id = torch.empty((n, H, W), dtype=torch.int32, device=dev)
+    if depth is None and want_depth:
+        depth = torch.empty((n, H, W), dtype=torch.float32, device=dev)
+    if face_id is not None:
+        _req(face_id, torch.int32, (n, H, W), "face_id")
+    if depth is not None:
+        _req(depth, torch.float32, (n, H, W), "depth")
+    with torch.cuda.device(dev):
+        check(_lib.lib().nb_mesh_render(ptr(vertices), ptr(normals), ptr(triangles), V, T, ptr(cams), n, H, W, ptr(out), ptr(face_id),
+                                        ptr(depth), ptr(scratch), int(scratch.numel()), _stream()), "nb_mesh_render")
+    extra = tuple(t for t in (face_id, depth) if t is not None)
+    return (out,) + extra if extra else out

@@ -22,6 +22,9 @@ class _LiveCfg:
 
     mesh_th = property(lambda self: float(cfg.mesh_th))
     result_dir = property(lambda self: cfg.result_dir)
+    mesh_render = property(lambda self: bool(getattr(cfg, "mesh_render", False)))  # not a reference key: off unless set
+    mesh_render_dataset = property(lambda self: str(getattr(cfg, "mesh_render_dataset", "zju_mocap")))
+    mesh_render_size = property(lambda self: tuple(int(v) for v in getattr(cfg, "mesh_render_size", (512, 512))))
 
 
 class Evaluator(_Evaluator):
