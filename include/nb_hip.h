@@ -269,7 +269,7 @@ int nb_composite_bwd(const float *raw, const float *z_vals, const float *ray_d, 
  * trans_a && trans_b is refused with NB_EINVAL, no caller of the path needs it).  Summation order: the trans_a form and the
  * colsum epilogue of nb_gemm_fused accumulate with fp32 atomics, so weight / bias gradients are reproducible to rounding
  * (~1e-7 relative), not bit for bit, from run to run — like the reference's own cuBLAS / atomics-based backward.  k == 0 is
- * an empty product: C = beta C (and the epilogue). */
+ * an empty product: C = beta C (and the epilogue); m == 0 or n == 0 is an empty result: NB_OK at once, no pointer is looked at. */
 int nb_sgemm(int trans_a, int trans_b, int32_t m, int32_t n, int32_t k, float alpha, const float *a, int32_t lda,
              const float *b, int32_t ldb, float beta, float *c, int32_t ldc, void *stream);
 /* (The non-transposed-A form with op(B) = B, >= 1024 rows, K a multiple of 32 and 16-byte aligned operands — the dX = dY . W
@@ -281,6 +281,13 @@ int nb_sgemm(int trans_a, int trans_b, int32_t m, int32_t n, int32_t k, float al
 int nb_gemm_fused(int trans_a, int trans_b, int32_t m, int32_t n, int32_t k, float alpha, const float *a, int32_t lda,
                   const float *b, int32_t ldb, float beta, float *c, int32_t ldc, const float *mask_y, int32_t ldy,
                   float *colsum, void *stream);
+
+/* Which kernel nb_gemm_fused / nb_sgemm launches for these arguments (host only, launches nothing; a and b count for their
+ * alignment only and are never dereferenced; NB_BWD_SPLIT is honoured as the launch honours it): 0 = none, op(A) = A^T with k == 0
+ * (C = beta C), 1 = split-K fp32 (op(A) = A^T), 2 = split-K bf16 pairs, 3 = the general fp32 kernel, 4 = the aligned fp32 kernel,
+ * 5 = the aligned fp32 kernel with op(B) = B^T, 6 = bf16 pairs (>= 1024 rows).  Sizes and flags are not validated here. */
+int nb_gemm_variant(int trans_a, int trans_b, int32_t m, int32_t n, int32_t k, const float *a, int32_t lda, const float *b,
+                    int32_t ldb);
 
 /* dy[i] = y[i] > 0 ? dy[i] : 0 (ReLU backward on the post-activation value), in place. */
 int nb_relu_bwd(float *dy, const float *y, int64_t n, void *stream);

@@ -97,6 +97,7 @@ SIGNATURES = {
     "nb_composite_bwd": (C.c_int, [_P, _P, _P, _I64, _I32, C.c_int, _P, _P, _P, _P, _P]),
     "nb_sgemm": (C.c_int, [C.c_int, C.c_int, _I32, _I32, _I32, C.c_float, _P, _I32, _P, _I32, C.c_float, _P, _I32, _P]),
     "nb_gemm_fused": (C.c_int, [C.c_int, C.c_int, _I32, _I32, _I32, C.c_float, _P, _I32, _P, _I32, C.c_float, _P, _I32, _P, _I32, _P, _P]),
+    "nb_gemm_variant": (C.c_int, [C.c_int, C.c_int, _I32, _I32, _I32, _P, _I32, _P, _I32]),
     "nb_relu_bwd": (C.c_int, [_P, _P, _I64, _P]),
     "nb_colsum": (C.c_int, [_P, _I64, _I32, _I32, _P, _P]),
     "nb_trilinear_bwd": (C.c_int, [C.POINTER(NbScene), C.c_void_p * 4, C.c_void_p * 4, _P, _P, _I64, _I32, _P]),

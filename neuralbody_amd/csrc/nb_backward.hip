@@ -668,7 +668,7 @@ int nb_composite_bwd(const float *raw, const float *z_vals, const float *ray_d, 
 
 int nb_sgemm(int trans_a, int trans_b, int32_t m, int32_t n, int32_t k, float alpha, const float *a, int32_t lda,
              const float *b, int32_t ldb, float beta, float *c, int32_t ldc, void *stream) {
-    NB_REQUIRE(c && (k == 0 || (a && b)) && m >= 0 && n >= 0 && k >= 0, "nb_sgemm: bad argument");
+    NB_REQUIRE(m >= 0 && n >= 0 && k >= 0, "nb_sgemm: bad sizes");
     if (m == 0 || n == 0) return NB_OK;
     return nb_gemm_fused(trans_a, trans_b, m, n, k, alpha, a, lda, b, ldb, beta, c, ldc, nullptr, 0, nullptr, stream);
 }
@@ -683,22 +683,58 @@ static bool bwd_split_enabled() {
     return on;
 }
 
+// The kernel nb_gemm_fused launches for a product (after beta's scale_matrix_kernel in the op(A) = A^T form): the one place that
+// decides it.  The operand pointers count for their alignment only.  The enum's order is the ABI of nb_gemm_variant.
+enum class GemmVariant {
+    SCALE_ONLY,   // op(A) = A^T with k == 0: C = beta C, no product kernel
+    TN,           // gemm_tn_kernel: split-K fp32
+    TN16,         // gemm_tn16_kernel: split-K, bf16 pairs
+    ROWS,         // gemm_rows_kernel: the general fp32 kernel
+    ROWS_FAST,    // gemm_rows_fast_kernel<false>
+    ROWS_FAST_T,  // gemm_rows_fast_kernel<true>: op(B) = B^T
+    ROWS16,       // gemm_rows16_kernel: bf16 pairs
+};
+
+static GemmVariant gemm_variant(int trans_a, int trans_b, int32_t m, int32_t n, int32_t k, const float *a, int32_t lda, const float *b,
+                                int32_t ldb) {
+    const bool aligned_rows = lda % 4 == 0 && ldb % 4 == 0 && ((uintptr_t)a % 16) == 0 && ((uintptr_t)b % 16) == 0;  // 16-byte aligned rows
+    if (trans_a) {
+        if (k == 0) return GemmVariant::SCALE_ONLY;
+        // weight-gradient shapes (M, N >= 32, thousands of rows, 16-byte aligned rows): bf16 pairs on the 16-bit matrix pipe
+        if (bwd_split_enabled() && m >= 32 && n >= 32 && k >= 1024 && aligned_rows) return GemmVariant::TN16;
+        return GemmVariant::TN;
+    }
+    // k == 0 (an empty product: C = beta C, then the epilogue) goes to the general kernel, whose loop is guarded; the fast
+    // kernel pre-loads its first operand panels before looking at k
+    const bool aligned = k > 0 && k % 16 == 0 && aligned_rows;
+    // the MLP backward's dX products (thousands of rows, K a multiple of 32, op(B) = B): bf16 pairs on the 16-bit matrix pipe
+    if (bwd_split_enabled() && aligned && !trans_b && k % 32 == 0 && m >= 1024) return GemmVariant::ROWS16;
+    if (aligned) return trans_b ? GemmVariant::ROWS_FAST_T : GemmVariant::ROWS_FAST;
+    return GemmVariant::ROWS;
+}
+
+int nb_gemm_variant(int trans_a, int trans_b, int32_t m, int32_t n, int32_t k, const float *a, int32_t lda, const float *b,
+                    int32_t ldb) {
+    return (int)gemm_variant(trans_a, trans_b, m, n, k, a, lda, b, ldb);
+}
+
 int nb_gemm_fused(int trans_a, int trans_b, int32_t m, int32_t n, int32_t k, float alpha, const float *a, int32_t lda,
                   const float *b, int32_t ldb, float beta, float *c, int32_t ldc, const float *mask_y, int32_t ldy,
                   float *colsum, void *stream) {
-    NB_REQUIRE(c && (k == 0 || (a && b)) && m >= 0 && n >= 0 && k >= 0, "nb_gemm_fused: bad argument");
-    if (m == 0 || n == 0) return NB_OK;
+    NB_REQUIRE(m >= 0 && n >= 0 && k >= 0, "nb_gemm_fused: bad sizes");
+    if (m == 0 || n == 0) return NB_OK;  // an empty result: nothing to compute, and an empty tensor's pointer may be NULL
+    NB_REQUIRE(c && (k == 0 || (a && b)), "nb_gemm_fused: NULL pointer");
     hipStream_t st = (hipStream_t)stream;
+    const GemmVariant variant = gemm_variant(trans_a, trans_b, m, n, k, a, lda, b, ldb);
     if (trans_a) {
         NB_REQUIRE(!trans_b && !mask_y && !colsum, "nb_gemm_fused: op(A) = A^T is the weight-gradient form (no epilogue, B not transposed)");
         if (beta != 1.f)
             hipLaunchKernelGGL(scale_matrix_kernel, dim3(nb_ceil_div((long long)m * n, 256)), dim3(256), 0, st, c, m, n, ldc, beta);
-        if (k == 0) {
+        if (variant == GemmVariant::SCALE_ONLY) {
             NB_CHECK_LAUNCH("scale_matrix_kernel");
             return NB_OK;
         }
-        // weight-gradient shapes (M, N >= 32, thousands of rows, 16-byte aligned rows): bf16 pairs on the 16-bit matrix pipe
-        if (bwd_split_enabled() && m >= 32 && n >= 32 && k >= 1024 && lda % 4 == 0 && ldb % 4 == 0 && ((uintptr_t)a % 16) == 0 && ((uintptr_t)b % 16) == 0) {
+        if (variant == GemmVariant::TN16) {
             hipLaunchKernelGGL(gemm_tn16_kernel, dim3(nb_ceil_div(m, 128), nb_ceil_div(n, 128), nb_ceil_div(k, TN16_ROWS)), dim3(256), 0,
                                st, a, lda, b, ldb, (long long)k, m, n, alpha, c, ldc);
             NB_CHECK_LAUNCH("gemm_tn16_kernel");
@@ -710,23 +746,22 @@ int nb_gemm_fused(int trans_a, int trans_b, int32_t m, int32_t n, int32_t k, flo
         return NB_OK;
     }
     const dim3 grid(nb_ceil_div(m, 128), nb_ceil_div(n, 128)), block(256);
-    // k == 0 (an empty product: C = beta C, then the epilogue) goes to the general kernel, whose loop is guarded; the fast
-    // kernel pre-loads its first operand panels before looking at k
-    const bool aligned = k > 0 && k % 16 == 0 && lda % 4 == 0 && ((uintptr_t)a % 16) == 0 && ldb % 4 == 0 && ((uintptr_t)b % 16) == 0;
-    // the MLP backward's dX products (thousands of rows, K a multiple of 32, op(B) = B): bf16 pairs on the 16-bit matrix pipe
-    if (bwd_split_enabled() && aligned && !trans_b && k % 32 == 0 && m >= 1024) {
+    switch (variant) {
+    case GemmVariant::ROWS16:
         hipLaunchKernelGGL(gemm_rows16_kernel, grid, block, 0, st, a, lda, b, ldb, (long long)m, k, n, alpha, beta, c, ldc, mask_y, ldy,
                            colsum);
         NB_CHECK_LAUNCH("gemm_rows16_kernel");
         return NB_OK;
-    }
-    if (aligned && trans_b)
+    case GemmVariant::ROWS_FAST_T:
         hipLaunchKernelGGL((gemm_rows_fast_kernel<true>), grid, block, 0, st, a, lda, b, ldb, (long long)m, k, n, alpha, beta, c, ldc, mask_y, ldy, colsum);
-    else if (aligned)
+        break;
+    case GemmVariant::ROWS_FAST:
         hipLaunchKernelGGL((gemm_rows_fast_kernel<false>), grid, block, 0, st, a, lda, b, ldb, (long long)m, k, n, alpha, beta, c, ldc, mask_y, ldy, colsum);
-    else
+        break;
+    default:
         hipLaunchKernelGGL(gemm_rows_kernel, grid, block, 0, st, a, lda, b, ldb, trans_b, (long long)m, k, n, alpha, beta, c, ldc,
                            mask_y, ldy, colsum);
+    }
     NB_CHECK_LAUNCH("gemm_rows_kernel");
     return NB_OK;
 }

@@ -815,6 +815,24 @@ def sgemm(a, b, trans_a=False, trans_b=False, out=None, alpha=1.0, beta=0.0, rel
     return out
 
 
+GEMM_VARIANTS = ("SCALE_ONLY", "TN", "TN16", "ROWS", "ROWS_FAST", "ROWS_FAST_T", "ROWS16")
+
+
+def gemm_variant(a, b, trans_a=False, trans_b=False):
+    """nb_gemm_variant: the kernel `sgemm(a, b, trans_a, trans_b)` launches, as a name of GEMM_VARIANTS (the enum's order);
+    "SCALE_ONLY" = trans_a with k == 0.  Nothing is launched and nothing is read: only the shapes, the row strides and the
+    alignment of the data pointers count, so host tensors do as well as device ones."""
+    for t, name in ((a, "a"), (b, "b")):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 2 or (t.shape[1] > 1 and t.stride(1) != 1):
+            raise ValueError("%s must be a 2-D fp32 tensor with unit column stride" % name)
+    m, k = (a.shape[1], a.shape[0]) if trans_a else (a.shape[0], a.shape[1])
+    k2, n = (b.shape[1], b.shape[0]) if trans_b else (b.shape[0], b.shape[1])
+    if k != k2:
+        raise ValueError("gemm_variant: inner dimensions %d vs %d" % (k, k2))
+    return GEMM_VARIANTS[int(_lib.lib().nb_gemm_variant(1 if trans_a else 0, 1 if trans_b else 0, m, n, k, ptr(a), a.stride(0),
+                                                        ptr(b), b.stride(0)))]
+
+
 def relu_bwd_(dy, y):
     """nb_relu_bwd in place: dy *= (y > 0); y is the post-activation value."""
     _req(dy, torch.float32, None, "dy")
