@@ -700,6 +700,49 @@ int nb_mesh_render(const float *verts, const float *normals, const int32_t *face
                    const float *cams, int32_t n_views, int32_t H, int32_t W, float *rgb, int32_t *face_id, float *depth,
                    void *scratch, int64_t scratch_bytes, void *stream);
 
+/* ---------------------------------------------------------------------------------
+ * A photographed frame on device — replaces the OpenCV calls between the image files and the kernels above:
+ * lib/datasets/light_stage/multi_view_dataset.py:58-64 (get_mask: cv2.erode, cv2.dilate, the border band), :129-142 (cv2.undistort
+ * of the float32 image and the uint8 mask, cv2.resize INTER_AREA / INTER_NEAREST by cfg.ratio, the background fill) and
+ * lib/datasets/light_stage/multi_view_mesh_dataset.py:102-109 (cv2.undistort of every view's mask).  The inputs are the files'
+ * BYTES (3 per pixel and 1 per pixel); no float image of the full resolution is ever written.  No allocation, no
+ * synchronisation, no atomics, everything on `stream`: the same inputs give the same bits.  "a (+) b" below is ONE IEEE operation
+ * rounded to nearest; no two are contracted into an FMA.
+ * nb_mask_band — get_mask (:58-64) for n_views label images at once, in one pass (no eroded or dilated image is written).
+ *   label, out dev [n_views,H,W] uint8, distinct.  m = (label != 0); e, d = the minimum and the maximum of m over the
+ *   border x border window centred on the pixel, pixels outside the image ignored (cv2's default border for both: the rule of
+ *   nb_mask_dilate); out = 100 where d - e == 1, else m.  border odd, 1..255; border = 1 gives m.
+ * nb_image_undistort — cv2.undistort(src, K, D) with newCameraMatrix = K (:129-130; mesh dataset :109), then the reduction by
+ *   the integer factor n = 1 / cfg.ratio (:136-138) and the fill (:139-142), for n_views views with a camera each.
+ *   rgb dev [n_views,H,W,3] uint8 or NULL; msk dev [n_views,H,W] uint8 or NULL (not both NULL); img_out dev
+ *   [n_views,H/n,W/n,3] fp32, NULL iff rgb is; msk_out dev [n_views,H/n,W/n] uint8, NULL iff msk is.
+ *   cam HOST [n_views, NB_CAM_DOUBLES] float64: fx fy cx cy k1 k2 p1 p2 k3 k4 k5 k6 (a 4-entry D has k3 = 0, a 4- or 5-entry D
+ *   k4 = k5 = k6 = 0), every entry finite, fx and fy non-zero.
+ *   Source position of full-resolution pixel (column j, row i), in float64, in this order:
+ *     x = (j (-) cx) (/) fx;  y = (i (-) cy) (/) fy;  x2 = x (*) x;  y2 = y (*) y;  r2 = x2 (+) y2;  _2xy = (2 (*) x) (*) y
+ *     kr = (1 (+) ((k3 (*) r2 (+) k2) (*) r2 (+) k1) (*) r2) (/) (1 (+) ((k6 (*) r2 (+) k5) (*) r2 (+) k4) (*) r2)
+ *     u = fx (*) ((x (*) kr (+) p1 (*) _2xy) (+) p2 (*) (r2 (+) 2 (*) x2)) (+) cx
+ *     v = fy (*) ((y (*) kr (+) p1 (*) (r2 (+) 2 (*) y2)) (+) p2 (*) _2xy) (+) cy
+ *   iu = rint(u (*) 32), iv = rint(v (*) 32) (half to even), clamped into int32, a NaN giving -2^31; sx = iu >> 5, sy = iv >> 5,
+ *   ax = iu & 31, ay = iv & 31: OpenCV's 1/32-pixel fixed-point map.  The taps are (sy, sx), (sy, sx+1), (sy+1, sx),
+ *   (sy+1, sx+1); a tap outside the image reads 0 (BORDER_CONSTANT).
+ *   uint8: w00 = (32-ay)(32-ax), w01 = (32-ay) ax, w10 = ay (32-ax), w11 = ay ax; value = (sum S w + 512) >> 10.
+ *   float: S = float(byte) (/) 255.f; gx = 1 (-) ax (/) 32.f, fx = ax (/) 32.f, likewise gy, fy; w00 = gy (*) gx, w01 = gy (*) fx,
+ *     w10 = fy (*) gx, w11 = fy (*) fx; value = ((S00 (*) w00 (+) S01 (*) w01) (+) S10 (*) w10) (+) S11 (*) w11 in fp32.
+ *   Reduction: msk_out(Y, X) = the undistorted mask at (nY, nX) (INTER_NEAREST by an integer factor); img_out(Y, X) = the fp32
+ *   sum, from 0 and in row-major order, of the n x n undistorted pixels of block (nY.., nX..), (*) (1.f (/) float(n n))
+ *   (INTER_AREA by an integer factor).  n >= 1 divides H and W; n = 1 copies.
+ *   fill: NB_FILL_NONE, or NB_FILL_BLACK / NB_FILL_WHITE: img_out = 0 / 1 where msk_out == 0 (needs msk).
+ *   n_views >= 1, 1 <= H, W <= 32768, 3 n_views H W <= 2^31 - 1, else NB_EINVAL.  One launch per 8 views, one thread per
+ *   output pixel. */
+#define NB_CAM_DOUBLES 12
+#define NB_FILL_NONE 0
+#define NB_FILL_BLACK 1
+#define NB_FILL_WHITE 2
+int nb_mask_band(const uint8_t *label, int32_t n_views, int32_t H, int32_t W, int32_t border, uint8_t *out, void *stream);
+int nb_image_undistort(const uint8_t *rgb, const uint8_t *msk, const double *cam, int32_t n_views, int32_t H, int32_t W, int32_t n,
+                       int fill, float *img_out, uint8_t *msk_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

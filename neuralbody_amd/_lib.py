@@ -17,6 +17,8 @@ ILL_SIGMA, ILL_T_MIN = 4e-3, 1e-6  # NB_ILL_SIGMA, NB_ILL_T_MIN
 SAMPLE_MODES = {"h36m": 0, "plain": 1}  # NB_SAMPLE_H36M, NB_SAMPLE_PLAIN
 PAD_MODES = {"zju": 0, "big_box": 1, "snapshot": 2}  # NB_PAD_ZJU, NB_PAD_BIG_BOX, NB_PAD_SNAPSHOT
 SMPL_JOINTS, SMPL_POSE_BASIS, SMPL_BETAS, SMPL_PARAMS, SMPL_WS_FLOATS = 24, 207, 10, 88, 512  # NB_SMPL_*
+CAM_DOUBLES = 12  # NB_CAM_DOUBLES
+FILL_MODES = {None: 0, "black": 1, "white": 2}  # NB_FILL_NONE, NB_FILL_BLACK, NB_FILL_WHITE
 
 
 def ill_scratch_bytes(cap):
@@ -139,6 +141,8 @@ SIGNATURES = {
     "nb_mesh_vertex_normals": (C.c_int, [_P, _P, _I32, _I32, _P, _P, _P]),
     "nb_mesh_render_scratch_size": (_I64, [_I32, _I32, _I32, _I32]),
     "nb_mesh_render": (C.c_int, [_P, _P, _P, _I32, _I32, _P, _I32, _I32, _I32, _P, _P, _P, _P, _I64, _P]),
+    "nb_mask_band": (C.c_int, [_P, _I32, _I32, _I32, _I32, _P, _P]),
+    "nb_image_undistort": (C.c_int, [_P, _P, C.POINTER(C.c_double), _I32, _I32, _I32, _I32, C.c_int, _P, _P, _P]),
 }
 
 _lib = None

@@ -73,6 +73,8 @@ class MeshLatticeDataset(torch.utils.data.Dataset):
         return int(self.source.n_items)
 
     def _dev(self, a, dtype):
+        if isinstance(a, torch.Tensor) and a.is_cuda:  # a source with a DeviceImagePrep: already where it belongs
+            return a
         return torch.from_numpy(np.ascontiguousarray(a, dtype=dtype)).to(self.device)
 
     def _cameras(self):
@@ -92,10 +94,11 @@ class MeshLatticeDataset(torch.utils.data.Dataset):
         msks, xyz, Rh, Th = self.source.load(index)
         fr = multi_view_frame(xyz, Rh, Th, cfg.voxel_size, cfg.big_box)
         axes = lattice_axes(fr["can_bounds"], cfg.voxel_size)
-        msks = np.ascontiguousarray(msks, dtype=np.uint8)
+        if not isinstance(msks, torch.Tensor):  # a device tensor: a source with a DeviceImagePrep made it there
+            msks = np.ascontiguousarray(msks, dtype=np.uint8)
         n_views = np.asarray(self.source.Ks).reshape(-1, 3, 3).shape[0]
         if msks.ndim != 3 or msks.shape[0] != n_views:
-            raise ValueError("item %d: masks %s for %d views" % (index, msks.shape, n_views))
+            raise ValueError("item %d: masks %s for %d views" % (index, tuple(msks.shape), n_views))
         return {"coord": fr["coord"], "out_sh": fr["out_sh"], "wbounds": fr["can_bounds"], "bounds": fr["bounds"], "R": fr["R"],
                 "Th": fr["Th"], "latent_index": min(index, cfg.num_train_frame - 1), "frame_index": index + cfg.begin_ith_frame,
                 "axis_x": axes[0], "axis_y": axes[1], "axis_z": axes[2], "msks": msks}
@@ -126,10 +129,13 @@ class MeshLatticeDataset(torch.utils.data.Dataset):
 class LightStageMeshSource:
     """The file side of lib/datasets/light_stage/multi_view_mesh_dataset.py, a thin restatement: the frame list and cameras
     (:22-45), the file number of a frame (:48-49), the two np.load calls of prepare_input (:52-54, :69-74) and get_mask
-    without its dilation (:102-109).  imageio and cv2 are imported on first use."""
+    without its dilation (:102-109).  imageio and cv2 are imported on first use.  `prep`: an image_prep.DeviceImagePrep to
+    undistort a frame's masks on the device instead (load() then returns them as one device tensor, and cv2 is never
+    imported); None keeps the cv2 lines."""
 
     def __init__(self, data_root, human, ann_file, training_view, begin_ith_frame, num_train_frame, num_render_frame=-1,
-                 vertices="vertices", params="params"):
+                 vertices="vertices", params="params", prep=None):
+        self.prep = prep
         self.data_root, self.human = data_root, human
         annots = np.load(ann_file, allow_pickle=True).item()
         cams = annots["cams"]
@@ -158,5 +164,9 @@ class LightStageMeshSource:
             i = i + 1
         xyz = np.load(os.path.join(self.data_root, self.vertices, "{}.npy".format(i))).astype(np.float32)
         params = np.load(os.path.join(self.data_root, self.params, "{}.npy".format(i)), allow_pickle=True).item()
-        msks = np.stack([self.get_mask(index, nv) for nv in range(self.ims.shape[1])])
+        if self.prep is None:
+            msks = np.stack([self.get_mask(index, nv) for nv in range(self.ims.shape[1])])
+        else:
+            paths = [os.path.join(self.data_root, "mask_cihp", im)[:-4] + ".png" for im in self.ims[index]]
+            msks = self.prep.masks(paths, self.Ks, self.Ds)
         return msks, xyz, params["Rh"], params["Th"]

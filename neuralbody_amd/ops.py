@@ -1320,3 +1320,71 @@ def mesh_render(vertices, normals, triangles, cams, H, W, out=None, want_face_id
                                         ptr(depth), ptr(scratch), int(scratch.numel()), _stream()), "nb_mesh_render")
     extra = tuple(t for t in (face_id, depth) if t is not None)
     return (out,) + extra if extra else out
+
+
+# ------------------------------------------------------------------------------------------- a photographed frame
+def mask_band(labels, border=5, out=None):
+    """nb_mask_band: get_mask of multi_view_dataset.py:58-64 for every label image of a device uint8 [V,H,W] stack -> a new
+    [V,H,W]: (label != 0), and 100 where the border x border erosion and dilation of it differ.  border = 1: (label != 0)."""
+    _req(labels, torch.uint8, (None, None, None), "labels")
+    border = int(border)
+    if border < 1 or border % 2 == 0 or border > 255:
+        raise ValueError("border must be odd, 1..255, got %d" % border)
+    if labels.numel() == 0:
+        raise ValueError("labels is empty: %s" % (tuple(labels.shape),))
+    if out is None:
+        out = torch.empty_like(labels)
+    _req(out, torch.uint8, tuple(labels.shape), "out")
+    if out.data_ptr() == labels.data_ptr():
+        raise ValueError("out is labels: the band is not computed in place")
+    V, H, W = (int(v) for v in labels.shape)
+    with torch.cuda.device(labels.device):
+        check(_lib.lib().nb_mask_band(ptr(labels), V, H, W, border, ptr(out), _stream()), "nb_mask_band")
+    return out
+
+
+def image_undistort(rgb, msk, cam, n=1, fill=None):
+    """nb_image_undistort: cv2.undistort(src, K, D), the reduction by the integer factor n (INTER_AREA for the image,
+    INTER_NEAREST for the mask) and the background fill of multi_view_dataset.py:129-142, from the files' bytes.
+    rgb: device uint8 [H,W,3] or [V,H,W,3], or None; msk: device uint8 [H,W] or [V,H,W], or None; cam: host float64 [12] or
+    [V,12], fx fy cx cy k1 k2 p1 p2 k3 k4 k5 k6 per view (image_prep.camera_constants); fill: None, 'black' or 'white' (the
+    image where the reduced mask is 0).  -> (img fp32 [(V,)H/n,W/n,3] or None, msk uint8 [(V,)H/n,W/n] or None)."""
+    import numpy as np
+
+    if rgb is None and msk is None:
+        raise ValueError("image_undistort: neither an image nor a mask")
+    if fill not in _lib.FILL_MODES:
+        raise ValueError("fill must be None, 'black' or 'white', got %r" % (fill,))
+    if fill is not None and (msk is None or rgb is None):
+        raise ValueError("fill = %r needs both an image and a mask" % (fill,))
+    cam = np.ascontiguousarray(np.asarray(cam, dtype=np.float64))
+    batched = cam.ndim == 2
+    if cam.ndim not in (1, 2) or cam.shape[-1] != _lib.CAM_DOUBLES:
+        raise ValueError("cam has shape %s, expected [12] or [V,12]" % (cam.shape,))
+    cam = cam.reshape(-1, _lib.CAM_DOUBLES)
+    V = int(cam.shape[0])
+    if V < 1 or not np.all(np.isfinite(cam)) or np.any(cam[:, :2] == 0.0):
+        raise ValueError("cam: at least one view, every constant finite, fx and fy non-zero")
+    lead = (V,) if batched else ()
+    first = rgb if rgb is not None else msk
+    if first.dim() < 2 + len(lead):
+        raise ValueError("%s has shape %s for cam %s" % ("rgb" if rgb is not None else "msk", tuple(first.shape), cam.shape))
+    H, W = (int(v) for v in first.shape[len(lead):len(lead) + 2])
+    if rgb is not None:
+        _req(rgb, torch.uint8, lead + (H, W, 3), "rgb")
+    if msk is not None:
+        _req(msk, torch.uint8, lead + (H, W), "msk")
+        if rgb is not None and msk.device != rgb.device:
+            raise ValueError("rgb and msk live on different devices")
+    n = int(n)
+    if H < 1 or W < 1 or H > 32768 or W > 32768 or 3 * V * H * W > 2 ** 31 - 1:
+        raise ValueError("no frame of V = %d, H = %d, W = %d (H, W 1..32768, 3 V H W at most 2^31 - 1)" % (V, H, W))
+    if n < 1 or H % n or W % n:
+        raise ValueError("n = %d must be >= 1 and divide H = %d and W = %d" % (n, H, W))
+    dev = first.device
+    img_out = torch.empty(lead + (H // n, W // n, 3), dtype=torch.float32, device=dev) if rgb is not None else None
+    msk_out = torch.empty(lead + (H // n, W // n), dtype=torch.uint8, device=dev) if msk is not None else None
+    with torch.cuda.device(dev):
+        check(_lib.lib().nb_image_undistort(ptr(rgb), ptr(msk), cam.ctypes.data_as(C.POINTER(C.c_double)), V, H, W, n,
+                                            _lib.FILL_MODES[fill], ptr(img_out), ptr(msk_out), _stream()), "nb_image_undistort")
+    return img_out, msk_out

@@ -17,6 +17,7 @@ if _ROOT not in sys.path:
 
 from lib.config import cfg  # noqa: E402
 
+from neuralbody_amd.image_prep import select_prep  # noqa: E402
 from neuralbody_amd.train_rays import LightStageFrameSource, TrainRayDataset  # noqa: E402
 
 
@@ -38,19 +39,22 @@ class _LiveCfg:
     seed = property(lambda self: int(getattr(cfg, "train_ray_seed", 0)))
 
 
-def disk_source(data_root, human, ann_file, split):
+def disk_source(data_root, human, ann_file, split, device="cuda:0"):
+    """`image_prep` is not a reference key (YAML only): 'cv2' prepares every image with OpenCV on the host as the reference does,
+    'device' with neuralbody_amd/image_prep.py, 'auto' (the default) with cv2 where it imports and on the device elsewhere."""
     return LightStageFrameSource(
         data_root, human, ann_file, split, training_view=list(cfg.training_view), begin_ith_frame=int(cfg.begin_ith_frame),
         frame_interval=int(cfg.frame_interval), num_train_frame=int(cfg.num_train_frame), H=int(cfg.H), W=int(cfg.W),
         ratio=cfg.ratio, mask_bkgd=bool(cfg.mask_bkgd), white_bkgd=bool(cfg.white_bkgd),
         vertices=getattr(cfg, "vertices", "vertices"), params=getattr(cfg, "params", "params"),
         test_novel_pose=bool(getattr(cfg, "test_novel_pose", False)),
-        num_novel_pose_frame=int(getattr(cfg, "num_novel_pose_frame", 0)))
+        num_novel_pose_frame=int(getattr(cfg, "num_novel_pose_frame", 0)),
+        prep=select_prep(str(getattr(cfg, "image_prep", "auto")), device))
 
 
 class Dataset(TrainRayDataset):
     def __init__(self, data_root, human, ann_file, split, source=None, device="cuda:0"):
         """`source`: a frame source to use instead of the files under `data_root` (tests)."""
-        super().__init__(source if source is not None else disk_source(data_root, human, ann_file, split), _LiveCfg(),
+        super().__init__(source if source is not None else disk_source(data_root, human, ann_file, split, device), _LiveCfg(),
                          split=split, device=device)
         self.data_root, self.human = data_root, human

@@ -17,6 +17,7 @@ if _ROOT not in sys.path:
 
 from lib.config import cfg  # noqa: E402
 
+from neuralbody_amd.image_prep import select_prep  # noqa: E402
 from neuralbody_amd.mesh_lattice import LightStageMeshSource, MeshLatticeDataset  # noqa: E402
 
 
@@ -31,11 +32,14 @@ class _LiveCfg:
     mesh_lattice_pts = property(lambda self: bool(getattr(cfg, "mesh_lattice_pts", False)))
 
 
-def disk_source(data_root, human, ann_file):
+def disk_source(data_root, human, ann_file, device="cuda:0"):
+    """`image_prep` is not a reference key (YAML only): 'cv2' undistorts the masks with OpenCV on the host as the reference does,
+    'device' with neuralbody_amd/image_prep.py, 'auto' (the default) with cv2 where it imports and on the device elsewhere."""
     return LightStageMeshSource(
         data_root, human, ann_file, training_view=list(cfg.training_view), begin_ith_frame=int(cfg.begin_ith_frame),
         num_train_frame=int(cfg.num_train_frame), num_render_frame=int(getattr(cfg, "num_render_frame", -1)),
-        vertices=getattr(cfg, "vertices", "vertices"), params=getattr(cfg, "params", "params"))
+        vertices=getattr(cfg, "vertices", "vertices"), params=getattr(cfg, "params", "params"),
+        prep=select_prep(str(getattr(cfg, "image_prep", "auto")), device))
 
 
 def _require_in_process():
@@ -53,5 +57,5 @@ class Dataset(MeshLatticeDataset):
     def __init__(self, data_root, human, ann_file, split, source=None, device="cuda:0"):
         """`source`: a frame source to use instead of the files under `data_root` (tests)."""
         _require_in_process()
-        super().__init__(source if source is not None else disk_source(data_root, human, ann_file), _LiveCfg(), device=device)
+        super().__init__(source if source is not None else disk_source(data_root, human, ann_file, device), _LiveCfg(), device=device)
         self.data_root, self.human, self.split = data_root, human, split

@@ -220,6 +220,8 @@ class TrainRayDataset(torch.utils.data.Dataset):
         return self._sampler
 
     def _dev(self, a, dtype):
+        if isinstance(a, torch.Tensor) and a.is_cuda:  # a source with a DeviceImagePrep: already where it belongs
+            return a
         return torch.from_numpy(np.ascontiguousarray(a, dtype=dtype)).to(self.device)
 
     def _frame(self, frame_index, xyz, Rh, Th):
@@ -277,11 +279,14 @@ class TrainRayDataset(torch.utils.data.Dataset):
 class LightStageFrameSource:
     """The file side of lib/datasets/light_stage/multi_view_dataset.py, a thin restatement: the item list (:22-50), get_mask
     (:54-66), the image / camera part of __getitem__ (:121-150) and the two np.load calls of prepare_input (:70-72, :87-92).
-    imageio and cv2 are imported on first use; everything here runs once per image."""
+    imageio and cv2 are imported on first use; everything here runs once per image.  `prep`: an image_prep.DeviceImagePrep
+    to do the image and mask work of load() on the device instead (load() then returns device tensors for both, and cv2 is
+    never imported); None keeps the cv2 lines."""
 
     def __init__(self, data_root, human, ann_file, split, training_view, begin_ith_frame, frame_interval, num_train_frame, H, W,
                  ratio, mask_bkgd, white_bkgd, vertices="vertices", params="params", test_novel_pose=False,
-                 num_novel_pose_frame=0):
+                 num_novel_pose_frame=0, prep=None):
+        self.prep = prep
         self.data_root, self.human, self.split = data_root, human, split
         annots = np.load(ann_file, allow_pickle=True).item()
         self.cams = annots["cams"]
@@ -316,6 +321,8 @@ class LightStageFrameSource:
         return msk
 
     def load(self, index):
+        if self.prep is not None:
+            return self._load_device(index)
         import cv2
         import imageio
 
@@ -334,6 +341,25 @@ class LightStageFrameSource:
             img[msk == 0] = 0
             if self.white_bkgd:
                 img[msk == 0] = 1
+        K[:2] = K[:2] * self.ratio
+        if self.human in ("CoreView_313", "CoreView_315"):
+            i = int(os.path.basename(img_path).split("_")[4])
+            frame_index = i - 1
+        else:
+            i = int(os.path.basename(img_path)[:-4])
+            frame_index = i
+        xyz = np.load(os.path.join(self.data_root, self.vertices, "{}.npy".format(i))).astype(np.float32)
+        params = np.load(os.path.join(self.data_root, self.params, "{}.npy".format(i)), allow_pickle=True).item()
+        return img, msk, K, R, T, frame_index, int(cam_ind), xyz, params["Rh"], params["Th"]
+
+    def _load_device(self, index):
+        """load() with `prep` standing where imageio and cv2 stand above: the same tuple, img and msk on the device."""
+        img_path = os.path.join(self.data_root, self.ims[index])
+        msk_path = os.path.join(self.data_root, "mask_cihp", self.ims[index])[:-4] + ".png"
+        cam_ind = self.cam_inds[index]
+        K, D = np.array(self.cams["K"][cam_ind]), np.array(self.cams["D"][cam_ind])
+        img, msk = self.prep.frame(img_path, msk_path, K, D, self.H, self.W, self.ratio, self.mask_bkgd, self.white_bkgd)
+        R, T = np.array(self.cams["R"][cam_ind]), np.array(self.cams["T"][cam_ind]) / 1000.0
         K[:2] = K[:2] * self.ratio
         if self.human in ("CoreView_313", "CoreView_315"):
             i = int(os.path.basename(img_path).split("_")[4])
