@@ -17,6 +17,7 @@
 #include <math.h>
 
 #include "nb_common.h"
+#include "nb_window.h"
 
 #pragma clang fp contract(off)
 
@@ -32,23 +33,12 @@ struct Cams {
     Cam c[MAX_VIEWS];
 };
 
-// msk = 100 where the window's maximum and minimum of (label != 0) differ, else (label != 0); pixels outside the image are ignored
-__global__ __launch_bounds__(256) void mask_band_kernel(const unsigned char *__restrict__ label, int H, int W, int half, long long n,
-                                                        unsigned char *__restrict__ out) {
-    const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= n) return;
-    const int x = (int)(p % W), y = (int)((p / W) % H);
-    const unsigned char *__restrict__ img = label + (p - (long long)y * W - x);  // the pixel's view
-    const int y0 = max(y - half, 0), y1 = min(y + half, H - 1), x0 = max(x - half, 0), x1 = min(x + half, W - 1);
+// the fold of nb_window.h for nb_mask_band: msk = 100 where the window's maximum and minimum of (label != 0) differ, else (label != 0)
+struct BandFold {
     unsigned any = 0, all = 1;
-    for (int yy = y0; yy <= y1; ++yy)
-        for (int xx = x0; xx <= x1; ++xx) {
-            const unsigned m = img[(long long)yy * W + xx] != 0;
-            any |= m;
-            all &= m;
-        }
-    out[p] = (unsigned char)(any != all ? 100u : (unsigned)(label[p] != 0));
-}
+    __device__ __forceinline__ void take(unsigned b) { any |= b != 0, all &= b != 0; }
+    __device__ __forceinline__ unsigned result(unsigned centre) const { return any != all ? 100u : (unsigned)(centre != 0); }
+};
 
 // rint(32 v) clamped into int32; a NaN becomes the lowest value (fmax returns its other operand)
 __device__ __forceinline__ int fixed32(double v) {
@@ -157,15 +147,7 @@ __global__ __launch_bounds__(BLOCK_X *BLOCK_Y) void image_undistort_kernel(const
 
 extern "C" int nb_mask_band(const uint8_t *label, int32_t n_views, int32_t H, int32_t W, int32_t border, uint8_t *out,
                             void *stream) {
-    NB_REQUIRE(label && out && label != out, "nb_mask_band: NULL pointer, or out is label");
-    NB_REQUIRE(n_views >= 1 && H >= 1 && W >= 1 && (long long)n_views * H * W <= 2147483647ll,
-               "nb_mask_band: n_views = %d, H = %d, W = %d (all >= 1, at most 2^31 - 1 pixels)", n_views, H, W);
-    NB_REQUIRE(border >= 1 && border % 2 == 1 && border <= 255, "nb_mask_band: border = %d (odd, 1..255)", border);
-    const long long n = (long long)n_views * H * W;
-    hipLaunchKernelGGL(mask_band_kernel, dim3(nb_ceil_div(n, 256)), dim3(256), 0, (hipStream_t)stream, label, H, W, border / 2, n,
-                       out);
-    NB_CHECK_LAUNCH("nb_mask_band");
-    return NB_OK;
+    return nbwindow::launch<BandFold>("nb_mask_band", "label", label, n_views, H, W, border, out, stream);
 }
 
 extern "C" int nb_image_undistort(const uint8_t *rgb, const uint8_t *msk, const double *cam, int32_t n_views, int32_t H, int32_t W,

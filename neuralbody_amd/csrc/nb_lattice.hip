@@ -12,6 +12,7 @@
 // count-and-place tile body (nb_scan_dev.h).  No atomics: the same inputs give the same bits.
 #include "nb_march_common.h"
 #include "nb_scan_dev.h"
+#include "nb_window.h"
 
 namespace {
 
@@ -76,19 +77,12 @@ struct GatherSeq {
     }
 };
 
-// out = max of the border x border neighbourhood around the pixel (anchor = centre), pixels outside the image ignored
-__global__ __launch_bounds__(256) void mask_dilate_kernel(const unsigned char *__restrict__ msk, int H, int W, int half, long long n,
-                                                          unsigned char *__restrict__ out) {
-    const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= n) return;
-    const int x = (int)(p % W), y = (int)((p / W) % H);
-    const unsigned char *__restrict__ img = msk + (p - (long long)y * W - x);  // the pixel's view
-    const int y0 = max(y - half, 0), y1 = min(y + half, H - 1), x0 = max(x - half, 0), x1 = min(x + half, W - 1);
+// the fold of nb_window.h for nb_mask_dilate: out = max of the window's bytes
+struct MaxFold {
     unsigned m = 0;
-    for (int yy = y0; yy <= y1; ++yy)
-        for (int xx = x0; xx <= x1; ++xx) m = max(m, (unsigned)img[(long long)yy * W + xx]);
-    out[p] = (unsigned char)m;
-}
+    __device__ __forceinline__ void take(unsigned b) { m = max(m, b); }
+    __device__ __forceinline__ unsigned result(unsigned) const { return m; }
+};
 
 __global__ __launch_bounds__(256) void lattice_scatter_kernel(const float *__restrict__ alpha, long long stride,
                                                               const int *__restrict__ lin, long long n, Lattice lat, unsigned n_pts,
@@ -115,15 +109,7 @@ long long lattice_points(const int32_t dims[3]) {
 
 extern "C" int nb_mask_dilate(const uint8_t *msk, int32_t n_views, int32_t H, int32_t W, int32_t border, uint8_t *out,
                               void *stream) {
-    NB_REQUIRE(msk && out && msk != out, "nb_mask_dilate: NULL pointer, or out is msk");
-    NB_REQUIRE(n_views >= 1 && H >= 1 && W >= 1 && (long long)n_views * H * W <= 2147483647ll,
-               "nb_mask_dilate: n_views = %d, H = %d, W = %d (all >= 1, at most 2^31 - 1 pixels)", n_views, H, W);
-    NB_REQUIRE(border >= 1 && border % 2 == 1 && border <= 255, "nb_mask_dilate: border = %d (odd, 1..255)", border);
-    const long long n = (long long)n_views * H * W;
-    hipLaunchKernelGGL(mask_dilate_kernel, dim3(nb_ceil_div(n, 256)), dim3(256), 0, (hipStream_t)stream, msk, H, W, border / 2, n,
-                       out);
-    NB_CHECK_LAUNCH("nb_mask_dilate");
-    return NB_OK;
+    return nbwindow::launch<MaxFold>("nb_mask_dilate", "msk", msk, n_views, H, W, border, out, stream);
 }
 
 extern "C" int nb_lattice_carve(const float *ax, const float *ay, const float *az, const int32_t dims[3], const nb_cull *cull,

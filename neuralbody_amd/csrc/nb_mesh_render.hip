@@ -19,16 +19,14 @@
 #include <math.h>
 
 #include "nb_common.h"
+#include "nb_raster.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
-constexpr int SUB = 256, HALF = SUB / 2;  // sub-pixel units per pixel; pixel (i, j) is sampled at (256 i + 128, 256 j + 128)
-static_assert(SUB == 1 << 8, "the pixel box divides by SUB with >> 8");
-constexpr float MAX_PIXEL = 32768.0f;     // a triangle with a vertex beyond it is skipped: every product below stays under 2^50
-constexpr int SMALL_BOX = 16;             // clipped boxes up to SMALL_BOX x SMALL_BOX are walked by one thread
-constexpr int LARGE_BLOCKS = 512;         // the large-triangle launch: a fixed grid striding over the device-side count
+// pixel (i, j) is sampled at (256 i + 128, 256 j + 128); a triangle with a vertex beyond MAX_PIXEL is skipped
+using nbraster::HALF, nbraster::MAX_PIXEL, nbraster::SUB;
 constexpr int CAM_FLOATS = 24;            // affine 3 x 4 | normal rotation 3 x 3 | 3 of padding
 constexpr float QUANT = 1048576.0f;       // 2^20: a unit face normal's component as an integer
 constexpr float NORM_EPS = 1e-8f;         // render_mesh.py:24
@@ -115,11 +113,10 @@ __device__ __forceinline__ unsigned ordered_bits(float d) {
 
 // A triangle of one view: its vertices through the view's affine, snapped, oriented to positive area; the attributes follow the
 // orientation.  The raster kernels and the resolve kernel both call this and so get the same bits.
-struct Tri {
+struct Tri : nbraster::Box {    // the box: the pixel centres inside the bounding box, clipped to the image
     int idx[3];                 // vertex indices in oriented order
     int px[3], py[3];           // snapped coordinates
     float d[3];                 // depths
-    int x0, x1, y0, y1;         // the pixel centres inside the bounding box, clipped to the image; empty when x0 > x1 or y0 > y1
     // the three edge functions at pixel (x, y)'s centre: e[i] belongs to the edge opposite vertex i, all >= 0 inside
     __device__ __forceinline__ void edges(int x, int y, long long e[3]) const {
         const long long X = (long long)x * SUB + HALF, Y = (long long)y * SUB + HALF;
@@ -155,20 +152,10 @@ __device__ __forceinline__ bool tri_setup(int tri, const int *__restrict__ faces
     }
     const long long area = (long long)(t.px[1] - t.px[0]) * (t.py[2] - t.py[0]) - (long long)(t.py[1] - t.py[0]) * (t.px[2] - t.px[0]);
     if (area == 0) return false;
-    if (area < 0) {
-        int s = t.idx[1];
-        t.idx[1] = t.idx[2], t.idx[2] = s;
-        s = t.px[1], t.px[1] = t.px[2], t.px[2] = s;
-        s = t.py[1], t.py[1] = t.py[2], t.py[2] = s;
-        const float f = t.d[1];
-        t.d[1] = t.d[2], t.d[2] = f;
-    }
-    const int minx = min(t.px[0], min(t.px[1], t.px[2])), maxx = max(t.px[0], max(t.px[1], t.px[2]));
-    const int miny = min(t.py[0], min(t.py[1], t.py[2])), maxy = max(t.py[0], max(t.py[1], t.py[2]));
-    // the centres 256 i + 128 inside [min, max]: ceil((min - 128) / 256) .. floor((max - 128) / 256)
-    t.x0 = max((minx + HALF - 1) >> 8, 0), t.x1 = min((maxx - HALF) >> 8, W - 1);
-    t.y0 = max((miny + HALF - 1) >> 8, 0), t.y1 = min((maxy - HALF) >> 8, H - 1);
-    return t.x0 <= t.x1 && t.y0 <= t.y1;
+    if (area < 0)
+        nbraster::swap(t.idx[1], t.idx[2]), nbraster::swap(t.px[1], t.px[2]), nbraster::swap(t.py[1], t.py[2]), nbraster::swap(t.d[1], t.d[2]);
+    // the centres 256 i + 128 inside the triangle's extent
+    return t.clip(t.px[0], t.py[0], t.px[1], t.py[1], t.px[2], t.py[2], -HALF, H, W);
 }
 
 // The sample of triangle t at pixel (x, y): false when the centre is not covered or the depth there is not finite.
@@ -189,51 +176,31 @@ __device__ __forceinline__ void offer(const Tri &t, int tri, int x, int y, unsig
     if (key < row[x]) atomicMin(row + x, key);  // the read is a hint (keys only fall): the atomic alone decides
 }
 
-// One thread per (view, triangle): small boxes are walked here, the others listed for raster_large_kernel.
-__global__ __launch_bounds__(256) void raster_small_kernel(const float *__restrict__ verts, const int *__restrict__ faces,
-                                                           const float *__restrict__ cams, int n, int T, int V, int H, int W,
-                                                           int *__restrict__ count, int *__restrict__ large,
-                                                           unsigned long long *__restrict__ keys) {
-    const int g = blockIdx.x * 256 + threadIdx.x;
-    const int view = g < n ? g / T : 0, tri = g - view * T;
-    Tri t;
-    const bool draw = g < n && tri_setup(tri, faces, verts, V, cams + (size_t)view * CAM_FLOATS, H, W, t);
-    const bool big = draw && (t.x1 - t.x0 >= SMALL_BOX || t.y1 - t.y0 >= SMALL_BOX);
-    // the wave's large triangles take consecutive list places: one atomic per wave that has any
-    const unsigned long long m = __ballot(big);
-    if (m) {
-        const int lane = threadIdx.x & 63, leader = __ffsll((long long)m) - 1;
-        int base = 0;
-        if (lane == leader) base = atomicAdd(count, __popcll(m));
-        base = __shfl(base, leader, 64);
-        if (big) large[base + __popcll(m & ((1ull << lane) - 1ull))] = g;  // < n places in all: every g is listed at most once
+// The triangle job of nb_raster.h: triangle g of the (view, triangle) ids, a key offered wherever it covers a pixel's centre.
+struct RasterJob : Tri {
+    const float *verts, *cams;
+    const int *faces;
+    int T, V, H, W;
+    unsigned long long *keys, *img;  // img, tri: the triangle's view and index, set by setup like the Tri
+    int tri;
+    __device__ __forceinline__ bool setup(int g) {
+        const int view = g / T;
+        tri = g - view * T, img = keys + (size_t)view * H * W;
+        return tri_setup(tri, faces, verts, V, cams + (size_t)view * CAM_FLOATS, H, W, *this);
     }
-    if (!draw || big) return;
-    unsigned long long *__restrict__ img = keys + (size_t)view * H * W;
-    for (int y = t.y0; y <= t.y1; ++y)
-        for (int x = t.x0; x <= t.x1; ++x) offer(t, tri, x, y, img + (size_t)y * W);
+    __device__ __forceinline__ void pixel(int x, int y) { offer(*this, tri, x, y, img + (size_t)y * W); }
+};
+
+__global__ __launch_bounds__(256) void raster_small_kernel(RasterJob job, unsigned long long *__restrict__ keys, int n,
+                                                           int *__restrict__ count, int *__restrict__ large) {
+    job.keys = keys;  // a parameter for its __restrict__ (nb_raster.h)
+    nbraster::small_pass(job, n, count, large);
 }
 
-// One workgroup per listed triangle, its threads striding over the clipped box.
-__global__ __launch_bounds__(256) void raster_large_kernel(const float *__restrict__ verts, const int *__restrict__ faces,
-                                                           const float *__restrict__ cams, int n, int T, int V, int H, int W,
-                                                           const int *__restrict__ count, const int *__restrict__ large,
-                                                           unsigned long long *__restrict__ keys) {
-    const int listed = min(*count, n);
-    for (int i = blockIdx.x; i < listed; i += gridDim.x) {
-        const int g = large[i];
-        if ((unsigned)g >= (unsigned)n) continue;
-        const int view = g / T, tri = g - view * T;
-        Tri t;
-        if (!tri_setup(tri, faces, verts, V, cams + (size_t)view * CAM_FLOATS, H, W, t)) continue;
-        unsigned long long *__restrict__ img = keys + (size_t)view * H * W;
-        const int bw = t.x1 - t.x0 + 1;
-        const long long px = (long long)bw * (t.y1 - t.y0 + 1);
-        for (long long p = threadIdx.x; p < px; p += 256) {
-            const int y = t.y0 + (int)(p / bw), x = t.x0 + (int)(p % bw);
-            offer(t, tri, x, y, img + (size_t)y * W);
-        }
-    }
+__global__ __launch_bounds__(256) void raster_large_kernel(RasterJob job, unsigned long long *__restrict__ keys, int n,
+                                                           const int *__restrict__ count, const int *__restrict__ large) {
+    job.keys = keys;  // a parameter for its __restrict__ (nb_raster.h)
+    nbraster::large_pass(job, n, count, large);
 }
 
 // One thread per pixel: the winner's sample again, by the functions that made the key, then its colour.
@@ -314,11 +281,10 @@ extern "C" int nb_mesh_render(const float *verts, const float *normals, const in
     NB_HIP(hipMemsetAsync(s.hdr, 0, HDR_BYTES, st));                       // the large-triangle count
     NB_HIP(hipMemsetAsync(s.keys, 0xFF, 8 * (size_t)n_px, st));            // every key: nothing drawn
     if (n_tri > 0) {
-        hipLaunchKernelGGL(raster_small_kernel, dim3(nb_ceil_div(n_tri, 256)), dim3(256), 0, st, verts, faces, cams, n_tri, T, V, H, W,
-                           s.hdr, s.large, s.keys);
+        const RasterJob job = {{}, verts, cams, faces, T, V, H, W};
+        hipLaunchKernelGGL(raster_small_kernel, dim3(nb_ceil_div(n_tri, 256)), dim3(256), 0, st, job, s.keys, n_tri, s.hdr, s.large);
         NB_CHECK_LAUNCH("nb_mesh_render (triangles)");
-        hipLaunchKernelGGL(raster_large_kernel, dim3(LARGE_BLOCKS), dim3(256), 0, st, verts, faces, cams, n_tri, T, V, H, W, s.hdr,
-                           s.large, s.keys);
+        hipLaunchKernelGGL(raster_large_kernel, dim3(nbraster::LARGE_BLOCKS), dim3(256), 0, st, job, s.keys, n_tri, s.hdr, s.large);
         NB_CHECK_LAUNCH("nb_mesh_render (large triangles)");
     }
     hipLaunchKernelGGL(resolve_kernel, dim3(nb_ceil_div(n_px, 256)), dim3(256), 0, st, verts, normals, faces, cams, n_px, T, V, H, W,

@@ -9,15 +9,13 @@
 // function of the inputs alone.  The output is a union of 1 bytes: racing identical stores, no ordering, the same bits every time.
 // The one atomic (a wave's slice of the large-triangle list) orders list entries, which no output bit depends on.
 #include "nb_march_common.h"
+#include "nb_raster.h"
 
 namespace {
 
-constexpr int SUB = 256, HALF = SUB / 2;      // sub-pixel units per pixel; a pixel is the closed square centre -+ HALF
-static_assert(SUB == 1 << 8, "tri_setup divides by SUB with >> 8");
+// a pixel is the closed square centre -+ HALF; |u|, |w| beyond MAX_PIXEL: the view does not cull
+using nbraster::HALF, nbraster::MAX_PIXEL, nbraster::SUB;
 constexpr float MIN_DEPTH = 0.01f;            // metres in front of the camera
-constexpr float MAX_PIXEL = 32768.0f;         // |u|, |w| beyond it: the view does not cull
-constexpr int SMALL_BOX = 16;                 // clipped bounding boxes up to SMALL_BOX x SMALL_BOX are walked by one thread
-constexpr int LARGE_BLOCKS = 512;             // the large-triangle launch: a fixed grid striding over the device-side count
 constexpr int HDR_COUNT = 0, HDR_FLAGS = 4;   // scratch header, int32: large-triangle count | pad | flag of every (frame, view)
 
 struct Scratch {
@@ -87,8 +85,7 @@ __global__ __launch_bounds__(256) void sil_fill_kernel(const int *__restrict__ f
 //   E_i(256 x, 256 y) + 128 (|dx_i| + |dy_i|) >= 0,
 // the largest value E_i takes on the closed square: the separating-axis test of square against triangle (the box is the other
 // two axes).
-struct Tri {
-    int x0, x1, y0, y1;          // clipped pixel box, empty when x0 > x1 or y0 > y1
+struct Tri : nbraster::Box {
     long long dx[3], dy[3], c[3];  // E_i(X, Y) = dx_i Y - dy_i X + c_i, the slack already in c_i
     __device__ __forceinline__ bool covers(int x, int y) const {
         const long long X = (long long)x * SUB, Y = (long long)y * SUB;
@@ -109,17 +106,9 @@ __device__ __forceinline__ bool tri_setup(int g, int Nf, int V, int H, int W, co
     int2 b = sv[ib], c = sv[ic];
     const long long area = (long long)(b.x - a.x) * (c.y - a.y) - (long long)(b.y - a.y) * (c.x - a.x);
     if (area == 0) return false;
-    if (area < 0) {
-        const int2 s = b;
-        b = c;
-        c = s;
-    }
-    const int minx = min(a.x, min(b.x, c.x)), maxx = max(a.x, max(b.x, c.x));
-    const int miny = min(a.y, min(b.y, c.y)), maxy = max(a.y, max(b.y, c.y));
-    // the squares 256 x -+ 128 that meet [minx, maxx]: ceil((minx - 128) / 256) .. floor((maxx + 128) / 256)
-    T.x0 = max((minx + HALF - 1) >> 8, 0), T.x1 = min((maxx + HALF) >> 8, W - 1);
-    T.y0 = max((miny + HALF - 1) >> 8, 0), T.y1 = min((maxy + HALF) >> 8, H - 1);
-    if (T.x0 > T.x1 || T.y0 > T.y1) return false;
+    if (area < 0) nbraster::swap(b, c);
+    // the squares 256 x -+ 128 that meet the triangle's extent
+    if (!T.clip(a.x, a.y, b.x, b.y, c.x, c.y, +HALF, H, W)) return false;
     const int2 P[3] = {a, b, c}, Q[3] = {b, c, a};
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
@@ -131,52 +120,27 @@ __device__ __forceinline__ bool tri_setup(int g, int Nf, int V, int H, int W, co
     return true;
 }
 
-// One thread per (frame, view, triangle): small boxes are walked here, the others listed for sil_large_kernel.
-__global__ __launch_bounds__(256) void sil_small_kernel(const int *__restrict__ faces, const int2 *__restrict__ snap,
-                                                        const int *__restrict__ flags, int n, int Nf, int V, int H, int W,
-                                                        int *__restrict__ count, int *__restrict__ large,
-                                                        unsigned char *__restrict__ out) {
-    const int g = blockIdx.x * 256 + threadIdx.x;
-    Tri T;
-    int fv = 0;
-    const bool draw = g < n && tri_setup(g, Nf, V, H, W, faces, snap, flags, T, fv);
-    const bool big = draw && (T.x1 - T.x0 >= SMALL_BOX || T.y1 - T.y0 >= SMALL_BOX);
-    // the wave's large triangles take consecutive list places: one atomic per wave that has any
-    const unsigned long long m = __ballot(big);
-    if (m) {
-        const int lane = threadIdx.x & 63, leader = __ffsll((long long)m) - 1;
-        int base = 0;
-        if (lane == leader) base = atomicAdd(count, __popcll(m));
-        base = __shfl(base, leader, 64);
-        if (big) large[base + __popcll(m & ((1ull << lane) - 1ull))] = g;  // < n places in all: every g is listed at most once
-    }
-    if (!draw || big) return;
-    unsigned char *__restrict__ img = out + (size_t)fv * H * W;
-    for (int y = T.y0; y <= T.y1; ++y)
-        for (int x = T.x0; x <= T.x1; ++x)
-            if (T.covers(x, y)) img[(size_t)y * W + x] = 1;
+// The triangle job of nb_raster.h: triangle g of the (frame, view, triangle) ids, a 1 byte wherever its pixel's square meets it.
+struct SilJob : Tri {
+    const int *faces, *flags;
+    const int2 *snap;
+    int Nf, V, H, W;
+    unsigned char *out;
+    int fv;  // the triangle's (frame, view), set by setup like the Tri
+    __device__ __forceinline__ bool setup(int g) { return tri_setup(g, Nf, V, H, W, faces, snap, flags, *this, fv); }
+    __device__ __forceinline__ void pixel(int x, int y) { if (covers(x, y)) out[((size_t)fv * H + y) * W + x] = 1; }
+};
+
+__global__ __launch_bounds__(256) void sil_small_kernel(SilJob job, unsigned char *__restrict__ out, int n, int *__restrict__ count,
+                                                        int *__restrict__ large) {
+    job.out = out;  // a parameter for its __restrict__ (nb_raster.h)
+    nbraster::small_pass(job, n, count, large);
 }
 
-// One workgroup per listed triangle, its threads striding over the clipped box.
-__global__ __launch_bounds__(256) void sil_large_kernel(const int *__restrict__ faces, const int2 *__restrict__ snap,
-                                                        const int *__restrict__ flags, int n, int Nf, int V, int H, int W,
-                                                        const int *__restrict__ count, const int *__restrict__ large,
-                                                        unsigned char *__restrict__ out) {
-    const int listed = min(*count, n);
-    for (int i = blockIdx.x; i < listed; i += gridDim.x) {
-        const int g = large[i];
-        if ((unsigned)g >= (unsigned)n) continue;
-        Tri T;
-        int fv;
-        if (!tri_setup(g, Nf, V, H, W, faces, snap, flags, T, fv)) continue;
-        unsigned char *__restrict__ img = out + (size_t)fv * H * W;
-        const int bw = T.x1 - T.x0 + 1;
-        const long long px = (long long)bw * (T.y1 - T.y0 + 1);
-        for (long long p = threadIdx.x; p < px; p += 256) {
-            const int y = T.y0 + (int)(p / bw), x = T.x0 + (int)(p % bw);
-            if (T.covers(x, y)) img[(size_t)y * W + x] = 1;
-        }
-    }
+__global__ __launch_bounds__(256) void sil_large_kernel(SilJob job, unsigned char *__restrict__ out, int n,
+                                                        const int *__restrict__ count, const int *__restrict__ large) {
+    job.out = out;  // a parameter for its __restrict__ (nb_raster.h)
+    nbraster::large_pass(job, n, count, large);
 }
 
 }  // namespace
@@ -208,11 +172,10 @@ extern "C" int nb_smpl_silhouette(const float *verts, const int32_t *faces, cons
     hipLaunchKernelGGL(sil_fill_kernel, dim3(nb_ceil_div(n_px, 16 * 256)), dim3(256), 0, st, flags, HW, n_px,
                        ((uintptr_t)out & 15) == 0 ? 1 : 0, out);
     NB_CHECK_LAUNCH("nb_smpl_silhouette (fill)");
-    hipLaunchKernelGGL(sil_small_kernel, dim3(nb_ceil_div(n_tri, 256)), dim3(256), 0, st, faces, s.snap, flags, n_tri, Nf, V, H, W, count,
-                       s.large, out);
+    const SilJob job = {{}, faces, flags, s.snap, Nf, V, H, W};
+    hipLaunchKernelGGL(sil_small_kernel, dim3(nb_ceil_div(n_tri, 256)), dim3(256), 0, st, job, out, n_tri, count, s.large);
     NB_CHECK_LAUNCH("nb_smpl_silhouette (triangles)");
-    hipLaunchKernelGGL(sil_large_kernel, dim3(LARGE_BLOCKS), dim3(256), 0, st, faces, s.snap, flags, n_tri, Nf, V, H, W, count, s.large,
-                       out);
+    hipLaunchKernelGGL(sil_large_kernel, dim3(nbraster::LARGE_BLOCKS), dim3(256), 0, st, job, out, n_tri, count, s.large);
     NB_CHECK_LAUNCH("nb_smpl_silhouette (large triangles)");
     return NB_OK;
 }

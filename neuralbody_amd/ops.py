@@ -24,11 +24,16 @@ def _stream():
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
-def _req(t, dtype, shape=None, name="tensor"):
+def _on_device(t, name):
     if not isinstance(t, torch.Tensor):
         raise TypeError("%s must be a torch.Tensor" % name)
     if not t.is_cuda:
         raise NbError("%s must live on a HIP device (got %s); the HIP path has no CPU fallback" % (name, t.device))
+    return t
+
+
+def _req(t, dtype, shape=None, name="tensor"):
+    _on_device(t, name)
     if t.dtype != dtype:
         raise ValueError("%s must be %s, got %s" % (name, dtype, t.dtype))
     if not t.is_contiguous():
@@ -964,6 +969,14 @@ def enc_scatter_codes_bwd(drows, rows_vert, n_rows, n_rows_max, n_codes, out=Non
     return dcodes
 
 
+def _cull_cams(RT, K, nv):
+    """The [nv,21] fp32 camera block of nb_cull and nb_smpl_silhouette: per view RT's 12 floats | K's 9."""
+    if not 1 <= nv <= 64:
+        raise ValueError("1..64 mask views supported, got %d" % nv)
+    cam = torch.cat([RT.detach().reshape(nv, 12).float(), K.detach().reshape(nv, 9).float()], 1).contiguous()
+    return _req(cam, torch.float32, (nv, 21), "cam")
+
+
 def make_cull(masks, RT, K, R0=None, Th0=None):
     """nb_cull from DEVICE tensors: masks [n_views,H,W] uint8 (non-zero = inside), RT [n_views,3,4], K [n_views,3,3]
     (batch['msks'][0], batch['RT'][0], batch['Ks'][0]); R0 [3,3] / Th0 [3] select the _msk variant (snapshot-frame
@@ -972,10 +985,7 @@ def make_cull(masks, RT, K, R0=None, Th0=None):
     masks = masks.contiguous()
     _req(masks, torch.uint8, (None, None, None), "masks")
     nv, H, W = (int(v) for v in masks.shape)
-    if not 1 <= nv <= 64:
-        raise ValueError("1..64 mask views supported, got %d" % nv)
-    cam = torch.cat([RT.detach().reshape(nv, 12).float(), K.detach().reshape(nv, 9).float()], 1).contiguous()
-    _req(cam, torch.float32, (nv, 21), "cam")
+    cam = _cull_cams(RT, K, nv)
     c = NbCull()
     c.n_views, c.H, c.W = nv, H, W
     c.pre_affine = 0 if R0 is None else 1
@@ -1011,21 +1021,28 @@ def lattice_scratch(dims, device):
     return scan_scratch(int(dims[0]) * int(dims[1]) * int(dims[2]), device)
 
 
-def mask_dilate(masks, border=5, out=None):
-    """nb_mask_dilate: cv2.dilate(m, ones((border, border))) of every mask of a device uint8 [V,H,W] stack -> a new [V,H,W]."""
-    _req(masks, torch.uint8, (None, None, None), "masks")
+def _window(entry, stack, name, border, out, in_place=None):
+    """nb_mask_dilate / nb_mask_band of a device uint8 [V,H,W] stack called `name` -> a new [V,H,W]; in_place: the ValueError text
+    for out = the stack (None: left to the library)."""
+    _req(stack, torch.uint8, (None, None, None), name)
     border = int(border)
     if border < 1 or border % 2 == 0 or border > 255:
         raise ValueError("border must be odd, 1..255, got %d" % border)
-    if masks.numel() == 0:
-        raise ValueError("masks is empty: %s" % (tuple(masks.shape),))
+    if stack.numel() == 0:
+        raise ValueError("%s is empty: %s" % (name, tuple(stack.shape)))
     if out is None:
-        out = torch.empty_like(masks)
-    _req(out, torch.uint8, tuple(masks.shape), "out")
-    V, H, W = (int(v) for v in masks.shape)
-    with torch.cuda.device(masks.device):
-        check(_lib.lib().nb_mask_dilate(ptr(masks), V, H, W, border, ptr(out), _stream()), "nb_mask_dilate")
+        out = torch.empty_like(stack)
+    _req(out, torch.uint8, tuple(stack.shape), "out")
+    if in_place and out.data_ptr() == stack.data_ptr():
+        raise ValueError(in_place)
+    with torch.cuda.device(stack.device):
+        check(getattr(_lib.lib(), entry)(ptr(stack), *stack.shape, border, ptr(out), _stream()), entry)
     return out
+
+
+def mask_dilate(masks, border=5, out=None):
+    """nb_mask_dilate: cv2.dilate(m, ones((border, border))) of every mask of a device uint8 [V,H,W] stack -> a new [V,H,W]."""
+    return _window("nb_mask_dilate", masks, "masks", border, out)
 
 
 def lattice_carve(axes, cull, scratch=None, inside=None, n_inside=None):
@@ -1077,11 +1094,7 @@ def lattice_scatter(alpha, lin, dims, pad, cube=None):
     """nb_lattice_scatter: alpha (device fp32 with n elements along ONE dimension, any stride: the [1,n,1] of calculate_density,
     or a column of a wider tensor) at the lattice points lin [n] int32 -> cube [X+2*pad, Y+2*pad, Z+2*pad] fp32, 0 elsewhere
     (a `cube` of the caller's must be zeroed)."""
-    if not isinstance(alpha, torch.Tensor):
-        raise TypeError("alpha must be a torch.Tensor")
-    if not alpha.is_cuda:
-        raise NbError("alpha must live on a HIP device (got %s); the HIP path has no CPU fallback" % (alpha.device,))
-    if alpha.dtype != torch.float32:
+    if _on_device(alpha, "alpha").dtype != torch.float32:
         raise ValueError("alpha must be torch.float32, got %s" % (alpha.dtype,))
     _req(lin, torch.int32, (None,), "lin")
     n = int(lin.shape[0])
@@ -1162,10 +1175,7 @@ def smpl_pose(model, params, new_params=False, verts=None, joints=None, ws=None)
 
 def _rows3(t, F, name):
     """A device fp32 [F,3] whose rows are contiguous (a column block of a wider row-major tensor included) -> its row stride."""
-    if not isinstance(t, torch.Tensor):
-        raise TypeError("%s must be a torch.Tensor" % name)
-    if not t.is_cuda:
-        raise NbError("%s must live on a HIP device (got %s); the HIP path has no CPU fallback" % (name, t.device))
+    _on_device(t, name)
     if t.dtype != torch.float32 or tuple(t.shape) != (F, 3) or t.stride(1) != 1 or (F > 1 and t.stride(0) < 3):
         raise ValueError("%s must be float32 [%d,3] with contiguous rows, got %s %s strides %s" % (name, F, t.dtype, tuple(t.shape),
                                                                                                 t.stride()))
@@ -1201,13 +1211,17 @@ def smpl_voxelize(verts, Rh, Th, voxel_size, pad="zju"):
 
 
 # ------------------------------------------------------------------------------------------- cull masks of a posed body
+def _raster_scratch(entry, dims, device, refusal):
+    n = int(getattr(_lib.lib(), entry)(*(int(d) for d in dims)))
+    if n <= 0:  # dimensions the library refuses
+        raise ValueError(refusal % dims)
+    return torch.empty(n, dtype=torch.uint8, device=device)
+
+
 def smpl_silhouette_scratch(F, V, Nf, nv, device):
     """Scratch of smpl_silhouette for F frames of V vertices and Nf triangles in nv views."""
-    n = int(_lib.lib().nb_smpl_silhouette_scratch_size(int(F), int(V), int(Nf), int(nv)))
-    if n <= 0:
-        raise ValueError("no silhouettes for F = %d, V = %d, Nf = %d, nv = %d (F 1..65535, nv 1..64, F nv V and F nv Nf < 2^31)" % (
-            F, V, Nf, nv))
-    return torch.empty(n, dtype=torch.uint8, device=device)
+    return _raster_scratch("nb_smpl_silhouette_scratch_size", (F, V, Nf, nv), device, "no silhouettes for F = %d, V = %d, Nf = %d, "
+                           "nv = %d (F 1..65535, nv 1..64, F nv V and F nv Nf < 2^31)")
 
 
 def smpl_silhouette(verts, faces, RT, K, H, W, out=None, scratch=None):
@@ -1222,20 +1236,13 @@ def smpl_silhouette(verts, faces, RT, K, H, W, out=None, scratch=None):
         raise ValueError("verts %s or faces %s is empty" % (tuple(verts.shape), tuple(faces.shape)))
     if not 1 <= H <= 32768 or not 1 <= W <= 32768:
         raise ValueError("H = %d, W = %d (1..32768)" % (H, W))
-    for name, t in (("RT", RT), ("K", K)):
-        if not isinstance(t, torch.Tensor):
-            raise TypeError("%s must be a torch.Tensor" % name)
-        if not t.is_cuda:
-            raise NbError("%s must live on a HIP device (got %s); the HIP path has no CPU fallback" % (name, t.device))
-    nv = int(K.shape[0])
-    if not 1 <= nv <= 64:
-        raise ValueError("1..64 mask views supported, got %d" % nv)
+    _on_device(RT, "RT")
+    nv = int(_on_device(K, "K").shape[0])
     if tuple(RT.shape) != (nv, 3, 4) or tuple(K.shape) != (nv, 3, 3):
         raise ValueError("RT %s, K %s: expected [%d,3,4] and [%d,3,3]" % (tuple(RT.shape), tuple(K.shape), nv, nv))
     if faces.device != dev or RT.device != dev or K.device != dev:
         raise ValueError("verts, faces, RT and K live on different devices")
-    cam = torch.cat([RT.detach().reshape(nv, 12).float(), K.detach().reshape(nv, 9).float()], 1).contiguous()
-    _req(cam, torch.float32, (nv, 21), "cam")
+    cam = _cull_cams(RT, K, nv)
     if scratch is None:
         scratch = smpl_silhouette_scratch(F, V, Nf, nv, dev)
     _req(scratch, torch.uint8, (None,), "scratch")
@@ -1275,11 +1282,8 @@ def mesh_vertex_normals(vertices, triangles, out=None, scratch=None):
 
 def mesh_render_scratch(n_views, H, W, T, device):
     """Scratch of mesh_render for n_views pictures of H x W pixels of T triangles."""
-    n = int(_lib.lib().nb_mesh_render_scratch_size(int(n_views), int(H), int(W), int(T)))
-    if n <= 0:
-        raise ValueError("no pictures for n_views = %d, H = %d, W = %d, T = %d (n_views >= 1, H, W 1..32768, n_views H W and "
-                         "n_views T < 2^31 - 256)" % (n_views, H, W, T))
-    return torch.empty(n, dtype=torch.uint8, device=device)
+    return _raster_scratch("nb_mesh_render_scratch_size", (n_views, H, W, T), device, "no pictures for n_views = %d, H = %d, W = %d, "
+                           "T = %d (n_views >= 1, H, W 1..32768, n_views H W and n_views T < 2^31 - 256)")
 
 
 def mesh_render(vertices, normals, triangles, cams, H, W, out=None, want_face_id=False, want_depth=False, scratch=None,
@@ -1326,21 +1330,7 @@ def mesh_render(vertices, normals, triangles, cams, H, W, out=None, want_face_id
 def mask_band(labels, border=5, out=None):
     """nb_mask_band: get_mask of multi_view_dataset.py:58-64 for every label image of a device uint8 [V,H,W] stack -> a new
     [V,H,W]: (label != 0), and 100 where the border x border erosion and dilation of it differ.  border = 1: (label != 0)."""
-    _req(labels, torch.uint8, (None, None, None), "labels")
-    border = int(border)
-    if border < 1 or border % 2 == 0 or border > 255:
-        raise ValueError("border must be odd, 1..255, got %d" % border)
-    if labels.numel() == 0:
-        raise ValueError("labels is empty: %s" % (tuple(labels.shape),))
-    if out is None:
-        out = torch.empty_like(labels)
-    _req(out, torch.uint8, tuple(labels.shape), "out")
-    if out.data_ptr() == labels.data_ptr():
-        raise ValueError("out is labels: the band is not computed in place")
-    V, H, W = (int(v) for v in labels.shape)
-    with torch.cuda.device(labels.device):
-        check(_lib.lib().nb_mask_band(ptr(labels), V, H, W, border, ptr(out), _stream()), "nb_mask_band")
-    return out
+    return _window("nb_mask_band", labels, "labels", border, out, in_place="out is labels: the band is not computed in place")
 
 
 def image_undistort(rgb, msk, cam, n=1, fill=None):

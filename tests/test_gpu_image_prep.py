@@ -30,7 +30,7 @@ def _same_bits(got, want):
 
 
 # ---------------------------------------------------------------------------------------------------------- 1. band
-@pytest.mark.parametrize("border", [1, 3, 5])
+@pytest.mark.parametrize("border", [1, 3, 5, 47])  # 47: a half width of 23 reaches past both sides of the image
 def test_band_matches_the_restatement(border):
     from neuralbody_amd import ops
 

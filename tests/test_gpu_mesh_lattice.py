@@ -191,7 +191,7 @@ def test_gather_beyond_the_fused_tile_count():
 
 
 # ---------------------------------------------------------------------------------------------------------- 4. dilate
-@pytest.mark.parametrize("border", [1, 3, 5])
+@pytest.mark.parametrize("border", [1, 3, 5, 107])  # 107: a half width of 53 reaches past both sides of the image
 def test_dilate_matches_the_restatement(border):
     from neuralbody_amd import ops
 

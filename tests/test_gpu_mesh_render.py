@@ -110,6 +110,13 @@ def _view(scale, cx, cy, R):
     return np.concatenate([M, R.reshape(-1), np.zeros(3)]).astype(np.float32)
 
 
+def _rotation(axis, ang):
+    """Rodrigues: the rotation by `ang` about `axis`."""
+    ax = np.array(axis) / np.linalg.norm(axis)
+    Kx = np.array([[0.0, -ax[2], ax[1]], [ax[2], 0.0, -ax[0]], [-ax[1], ax[0], 0.0]])
+    return np.eye(3) + math.sin(ang) * Kx + (1.0 - math.cos(ang)) * Kx @ Kx
+
+
 @functools.lru_cache(maxsize=None)
 def _path_case():
     """The tetrahedron of the silhouette suite in five views at 96 x 128: filling the image (boxes far beyond 16 x 16: a workgroup
@@ -117,9 +124,7 @@ def _path_case():
     vertex beyond +-32768 px: skipped).  The faces hold both windings, a repeated-vertex face of zero area, a triangle lying behind
     the body (face 6) and a second copy of face 0 (face 7)."""
     v, faces = sil.tetrahedron(0.25)
-    ax, ang = np.array([1.0, -1.0, 0.2]) / np.linalg.norm([1.0, -1.0, 0.2]), 0.9  # three faces towards the camera
-    Kx = np.array([[0.0, -ax[2], ax[1]], [ax[2], 0.0, -ax[0]], [-ax[1], ax[0], 0.0]])
-    R = np.eye(3) + math.sin(ang) * Kx + (1.0 - math.cos(ang)) * Kx @ Kx
+    R = _rotation((1.0, -1.0, 0.2), 0.9)  # three faces towards the camera
     behind = np.array([[-0.05, -0.04, -1.0], [0.06, -0.03, -1.0], [0.0, 0.05, -1.0]]) @ R  # rows R^T p: view space z = -1, depth 1
     verts = np.concatenate([v, behind]).astype(np.float32)
     faces = np.concatenate([faces[:2], faces[2:, ::-1], [[1, 1, 3], [2, 0, 2], [4, 5, 6], faces[0]]]).astype(np.int32)
@@ -154,6 +159,28 @@ def test_large_small_clipped_degenerate_coincident_and_hidden_triangles():
     for pair, want_ids in ((faces[6:7], {-1, 0}), (faces[[0, 0]], {-1, 0})):
         alone = ops.mesh_render(tv, normals, _dev(pair), tc[:1], PATH_H, PATH_W, want_face_id=True)[1]
         assert set(np.unique(_bits(alone)).tolist()) == want_ids
+
+
+def test_more_listed_triangles_than_workgroups():
+    """320 faces in two views at 256 x 256: more than 512 boxes of 17 or more pixel centres on a side, so the fixed grid of the
+    large-triangle launch strides over its list and whole waves append to it."""
+    from neuralbody_amd import ops
+
+    v, f = sil.icosphere(2, sil.ELLIPSOID)
+    cams = np.stack([_view(250.0, 127.3, 128.6, _rotation(axis, ang)) for axis, ang in (((1.0, -1.0, 0.2), 0.9), ((0.1, 1.0, 0.3), 2.1))])
+    large = 0
+    for cam in cams:
+        px = mr._project64(v, cam)[:, :2][f]  # [T,3,2]
+        lo, hi = np.ceil(px.min(axis=1) - 0.5), np.floor(px.max(axis=1) - 0.5)
+        large += int(((hi - lo).max(axis=1) >= 16).sum())
+    print("%d of %d (view, triangle) boxes are large" % (large, 2 * len(f)))
+    assert len(f) == 320 and large > 512
+    tv, tf, tc = _dev(v), _dev(f), _dev(cams)
+    normals = ops.mesh_vertex_normals(tv, tf)
+    got = ops.mesh_render(tv, normals, tf, tc, 256, 256, want_face_id=True, want_depth=True)
+    want = mr.snapped_stack(v, _bits(normals), f, cams, 256, 256)
+    for name, g, ref in zip(("rgb", "face_id", "depth"), got, want):
+        assert _same(_bits(g), ref), name
 
 
 # ---------------------------------------------------------------------------------------------------------- 4. refusals

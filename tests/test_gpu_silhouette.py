@@ -84,6 +84,26 @@ def test_large_small_clipped_and_degenerate_triangles():
     assert torch.equal(_masks(plain), got)
 
 
+def test_more_listed_triangles_than_workgroups():
+    """320 faces in two views at 256 x 256: more than 512 boxes of 17 or more pixels on a side, so the fixed grid of the
+    large-triangle launch strides over its list and whole waves append to it."""
+    v, faces = sil.icosphere(2, sil.ELLIPSOID)
+    Ks, RTs = sil.orbit((0.2, 1.4), 1.5, 1.3 * 256, 256, 256)
+    large = 0
+    for view in range(2):
+        uv = sil.project(v, Ks[view], RTs[view])[0][faces]  # [Nf,3,2]
+        lo, hi = np.ceil(uv.min(axis=1) - 0.5), np.floor(uv.max(axis=1) + 0.5)
+        assert lo.min() >= 0 and hi.max() <= 255  # all on the image
+        large += int(((hi - lo).max(axis=1) >= 16).sum())
+    print("%d of %d (view, triangle) boxes are large" % (large, 2 * len(faces)))
+    assert len(faces) == 320 and large > 512
+    c = dict(verts=v[None], faces=faces, Ks=Ks, RTs=RTs, H=256, W=256)
+    lo, hi = sil.lo_hi_stack(c["verts"], faces, Ks, RTs, 256, 256)
+    assert sil.band_fraction(lo, hi) <= sil.BAND_CAP
+    m = _check_band("ico320 at 256 x 256", _masks(c), lo, hi)
+    assert np.array_equal(m, sil.snapped_stack(c["verts"], faces, Ks, RTs, 256, 256).astype(bool))
+
+
 # ---------------------------------------------------------------------------------------------------------- 3. views that do not cull
 def test_a_view_too_near_or_too_wide_is_all_ones_and_leaves_the_others_alone():
     c, _, _ = _case("ico320")
