@@ -44,8 +44,9 @@ using namespace nbm;
 namespace {
 
 // ---------------------------------------------------------------- weight stream (per wave), in 1-KiB pieces
-// phase = NB K blocks x MT output tiles of this wave; per block: for each of its 4 chunks, for each tile: A16 (1 piece: the fp16
-// heads, the main product); then its two CROSS TERMS in execution order, for each tile one fragment: k = 0 W_h (multiplies the
+// phase = NB K blocks x MT output tiles of this wave (wave w's b-th block of a phase over published activations is LDS block
+// (b + w) & 3: it starts with the block it has published itself, layer_s); per block: for each of its 4 chunks, for each tile:
+// A16 (1 piece: the fp16 heads, the main product); then its two CROSS TERMS in execution order, for each tile one fragment: k = 0 W_h (multiplies the
 // remainder operand), k = 1 W_l (multiplies the head operand).  A cross fragment is fp6 e2m3 — 24 bytes of data + its E8M0 scale
 // in the lane's seventh dword, 2 pieces — or, for the terms in NB_FP4_TERMS (bit k), fp4 e2m1 — 16 bytes of data, 1 piece, its
 // scale one byte of the block's SCALE DWORD (byte k MT + m; one 256-byte load per block from behind the pieces).  The cross
@@ -285,7 +286,7 @@ __device__ __forceinline__ void ring_prime(const WSrc &wl, WRing &ring) {
     sfor<0, S_R>([&](auto pc) { ring_put<P0 + decltype(pc)::value>(ring, load_piece(wl, P0 + decltype(pc)::value)); });
 }
 
-// acc[m][n] += W[tiles of this wave, K range of the phase] . X for the NB blocks at LDS blocks 0..NB-1
+// acc[m][n] += W[tiles of this wave, K range of the phase] . X for the NB blocks at LDS blocks 0..NB-1 (OWN: below)
 // AHEAD: the last S_R pieces' slots are refilled with the first pieces of the FOLLOWING phase (otherwise: ring_prime).
 // A phase is a flat list of steps, six per block: the block's four K=16 chunks (MT x 2 fp16 MFMAs each), then its two cross
 // terms (k = 0: W_h (fp6) x remainders, LDS form 1; k = 1: W_l x heads, form 0; MT x 2 scaled MFMAs each).  The B operands
@@ -294,20 +295,39 @@ struct BOps {
     i32x4 m[2][2];  // [buffer][N tile]: main
     i32x8 c[2][2];  // cross: 6 registers of bf6 data, the scale byte in register 6
 };
+// an LDS block's operands lie BLOCK_BYTES apart in both sections (four head chunks | 2 forms x 2 N tiles of bf6 fragments), so one
+// address per block — the lane's slot in the block's first chunk — reaches all six steps' operands through immediate offsets
+constexpr int BLOCK_BYTES = 4 * CH_BYTES;
+static_assert(BLOCK_BYTES == 2 * 2 * F6_BYTES, "one block stride for the head chunks and the bf6 fragments");
 template <int T>
-__device__ __forceinline__ void read_b(const char *b16, const char *b6, BOps &x) {
-    constexpr int b = T / 6, j = T % 6, buf = T & 1;
+__device__ __forceinline__ void read_b(const char *blk, BOps &x) {  // step T's operands of the LDS block whose lane slot is blk
+    constexpr int j = T % 6, buf = T & 1;
     if constexpr (j < 4) {
-        constexpr int c = 4 * b + j;
-        x.m[buf][0] = *reinterpret_cast<const i32x4 *>(b16 + c * CH_BYTES);
-        x.m[buf][1] = *reinterpret_cast<const i32x4 *>(b16 + c * CH_BYTES + 1024);
+        x.m[buf][0] = *reinterpret_cast<const i32x4 *>(blk + j * CH_BYTES);
+        x.m[buf][1] = *reinterpret_cast<const i32x4 *>(blk + j * CH_BYTES + 1024);
     } else {
         constexpr int form = 1 - TERM_ORDER[j - 4];  // W_h multiplies the remainders (form 1), W_l the heads (form 0)
 #pragma unroll
         for (int n = 0; n < 2; ++n) {
-            const char *q = b6 + ((b * 2 + form) * 2 + n) * F6_BYTES;
+            const char *q = blk + ACT6_OFF + (form * 2 + n) * F6_BYTES;
             const i32x4 lo = *reinterpret_cast<const i32x4 *>(q), hi4 = *reinterpret_cast<const i32x4 *>(q + 1024);
             x.c[buf][n] = i32x8{lo.x, lo.y, lo.z, lo.w, hi4.x, hi4.y, hi4.z, hi4.w};
+        }
+    }
+}
+// the same operands straight from the half-blocks a lane has just converted (publish_s): store_halfblock puts every 16-byte piece
+// of h[n] into the lane's own slot (kh * 32 + slot = lane) of block `wave`, which is where read_b would find it again
+template <int T>
+__device__ __forceinline__ void own_b(const HalfBlock (&h)[2], BOps &x) {
+    constexpr int j = T % 6, buf = T & 1;
+#pragma unroll
+    for (int n = 0; n < 2; ++n) {
+        if constexpr (j < 4) {
+            x.m[buf][n] = __builtin_bit_cast(i32x4, h[n].xh[j]);
+        } else if constexpr (1 - TERM_ORDER[j - 4] == 0) {
+            x.c[buf][n] = i32x8{h[n].xx[0], h[n].xx[1], h[n].xx[2], h[n].xx[3], h[n].xx[4], h[n].xx[5], h[n].eb, 0};
+        } else {
+            x.c[buf][n] = i32x8{h[n].xl[0], h[n].xl[1], h[n].xl[2], h[n].xl[3], h[n].xl[4], h[n].xl[5], h[n].eb - 11, 0};
         }
     }
 }
@@ -317,21 +337,51 @@ struct NoFill {
 };
 // FILL: independent VALU work cut into 6 NB slices; slice t is issued right behind the MFMAs of step t (VALU instructions of
 // the SAME wave execute under its MFMAs; another wave's do not: profiles/r03_ms6_coexec.md)
-template <int P0, int MT, int NB, bool AHEAD, class Fill = NoFill>
-__device__ __forceinline__ void layer_s(const WSrc &wl, const char *act, int lane, WRing &ring, f32x16 (&acc)[2][2], Fill fill = Fill()) {
+//
+// OWN (the phases over PUBLISHED activations: `own` = the half-blocks this wave has converted, publish_s): the wave walks the K
+// blocks from its own one, step block b = LDS block (b + wave) & 3 — the pack kernel lays the wave's pieces and scale dwords out
+// in that order — and takes the six steps of its first block from `own` in registers.  It stores `own` for the other waves HERE,
+// behind the caller's bias reads (LDS serves a wave in order: a read issued behind the 16 stores waits for all of them), and
+// needs the other waves' blocks from the first read of the second block on, issued one step ahead like every read: the barrier
+// that makes the publishes visible stands right in front of it.  Stores, barrier and LDS turnaround lie under the first block's
+// MFMAs.  ST: stamps of the experiment builds (0: none).
+template <int P0, int MT, int NB, bool AHEAD, bool OWN, int ST = 0, class Fill = NoFill>
+__device__ __forceinline__ void layer_s(const WSrc &wl, char *act, int lane, int wave, const HalfBlock (&own)[2], WRing &ring,
+                                        f32x16 (&acc)[2][2], unsigned *tbuf = nullptr, Fill fill = Fill()) {
     constexpr int PPB = block_pieces(MT);  // pieces per block
     constexpr int PEND = P0 + NB * PPB;
     constexpr int NT = 6 * NB;
     constexpr int S0 = phase_s0(phase_of_p0(P0));
-    const char *b16 = act + lane * 16;
-    const char *b6 = act + ACT6_OFF + lane * 16;
+    static_assert(!OWN || NB == 4, "the rotation is over the four published blocks");
+    const char *slot0 = act + lane * 16;
+    // the lane's slot in the LDS block of step block b: the block offset is wave-uniform (one scalar add per block)
+    auto block_at = [&](int b) -> const char * { return slot0 + (OWN ? ((b + wave) & 3) : b) * BLOCK_BYTES; };
+    const char *blk = slot0;
     BOps x;
     int sc[2] = {0, 0};  // scale dwords of the blocks' four-bit fragments: block b in sc[b & 1], loaded one block ahead
     if constexpr (ANY_FP4) sc[0] = load_scales(wl, S0);
-    read_b<0>(b16, b6, x);
+    if constexpr (OWN) {
+        if constexpr (ST != 0) {  // the bias has arrived: the first MFMA can issue
+            NB_HOOK_LAYER_FIRST_READ(acc[0][0], acc[0][1]);
+            FOLD_SUB(ST);
+        }
+#pragma unroll
+        for (int n = 0; n < 2; ++n) store_halfblock(act, wave, lane >> 5, n, lane & 31, own[n]);
+        if constexpr (ST != 0) FOLD_SUB(ST - 2);
+    } else {
+        read_b<0>(blk, x);
+    }
     sfor<0, NT>([&](auto tc) {
         constexpr int t = decltype(tc)::value, b = t / 6, j = t % 6, buf = t & 1;
-        if constexpr (t + 1 < NT) read_b<t + 1>(b16, b6, x);
+        if constexpr (OWN && t < 6) own_b<t>(own, x);
+        if constexpr (t + 1 < NT && !(OWN && t + 1 < 6)) {
+            if constexpr ((t + 1) % 6 == 0) blk = block_at((t + 1) / 6);
+            if constexpr (OWN && t + 1 == 6) {
+                __syncthreads();  // every wave's publish is visible
+                if constexpr (ST != 0) FOLD_SUB(ST - 1);
+            }
+            read_b<t + 1>(blk, x);
+        }
         if constexpr (ANY_FP4 && j == 0 && b + 1 < NB) sc[(b + 1) & 1] = load_scales(wl, S0 + b + 1);
         if constexpr (j < 4) {
             sfor<0, MT>([&](auto mc) {
@@ -388,10 +438,9 @@ __device__ __forceinline__ void init_bias(const float *bp, int tile0, int hi, f3
 
 // relu'd accumulators of this wave (two tiles x two N tiles) -> K block `wave` of the next layer, in place: the lane's 16 +
 // 16 values of an N tile are half-block (wave, hi) and go into the lane's own fragment slot.  The conversion runs BEFORE the
-// barrier that retires the previous activations (it needs this wave's accumulators only), the stores behind it.
-__device__ __forceinline__ void publish_s(char *act, int lane, int wave, f32x16 (&acc)[2][2]) {
-    const int i = lane & 31, hi = lane >> 5;
-    HalfBlock h[2];
+// barrier that retires the previous activations (it needs this wave's accumulators only).  The stores (behind that barrier) and
+// the barrier that makes them visible are the following layer_s's: its first block's operands are `h` itself.
+__device__ __forceinline__ void publish_s(f32x16 (&acc)[2][2], HalfBlock (&h)[2]) {
 #pragma unroll
     for (int n = 0; n < 2; ++n) {
 #pragma unroll
@@ -401,9 +450,6 @@ __device__ __forceinline__ void publish_s(char *act, int lane, int wave, f32x16 
         h[n] = convert_halfblock<false>([&](int q) { return q < 16 ? acc[0][n][q & 15] : acc[1][n][q & 15]; });
     }
     __syncthreads();  // every wave is done reading the previous activations
-#pragma unroll
-    for (int n = 0; n < 2; ++n) store_halfblock(act, wave, hi, n, i, h[n]);
-    __syncthreads();
 }
 
 // ---------------------------------------------------------------- the folded first layer
@@ -1123,7 +1169,8 @@ __global__ __launch_bounds__(256, 2) void nb_march_fold_kernel(MarchArgs a, cons
             FOLD_DUMP(0, 2)
             FOLD_STAMP(2);
             ring_prime<P_L1>(wl, ring);
-            publish_s(actz, lane_i, wave, acc);
+            HalfBlock own[2];  // what this wave has published: the first K block of the layer that follows
+            publish_s(acc, own);
             FOLD_STAMP(3);
             // ---- fc_1, fc_2
             init_bias<2>(pk + P_B1, 2 * wave, hi, acc);
@@ -1158,17 +1205,17 @@ __global__ __launch_bounds__(256, 2) void nb_march_fold_kernel(MarchArgs a, cons
                         conv6_pair<2 * i + 1>(pec, e[4 * i + 2], e[4 * i + 3]);
                     }
                 };
-                if constexpr (DENSITY_ONLY) layer_s<P_L1, 2, 4, true>(wl, actz, lane_i, ring, acc);
-                else layer_s<P_L1, 2, 4, true>(wl, actz, lane_i, ring, acc, pe_fill);
+                if constexpr (DENSITY_ONLY) layer_s<P_L1, 2, 4, true, true, 24>(wl, actz, lane_i, wave, own, ring, acc, NB_HOOK_TBUF);
+                else layer_s<P_L1, 2, 4, true, true, 24>(wl, actz, lane_i, wave, own, ring, acc, NB_HOOK_TBUF, pe_fill);
             }
             HalfBlock peh;
             if constexpr (!DENSITY_ONLY) peh = conv6_finish(pec);
             FOLD_DUMP(1, 2)
             FOLD_STAMP(4);
-            publish_s(actz, lane_i, wave, acc);
+            publish_s(acc, own);
             FOLD_STAMP(5);
             init_bias<2>(pk + P_B2, 2 * wave, hi, acc);
-            layer_s<P_L2, 2, 4, true>(wl, actz, lane_i, ring, acc);
+            layer_s<P_L2, 2, 4, true, true, 27>(wl, actz, lane_i, wave, own, ring, acc, NB_HOOK_TBUF);
             FOLD_DUMP(2, 2)
             FOLD_STAMP(6);
             // ---- the next step's sample: depth, grid coordinates, silhouette test, (wave, level) boxes — published by the
@@ -1192,7 +1239,7 @@ __global__ __launch_bounds__(256, 2) void nb_march_fold_kernel(MarchArgs a, cons
 #pragma unroll
                         for (int r = 0; r < 16; ++r) acc[m][n][r] = relu1(acc[m][n][r]);
             } else {
-                publish_s(actz, lane_i, wave, acc);  // acc now holds relu(h3)
+                publish_s(acc, own);  // acc now holds relu(h3)
             }
             FOLD_STAMP(8);
             // ---- alpha_fc: partial dot product over this wave's 64 features, finished by the owner lanes
@@ -1235,7 +1282,7 @@ __global__ __launch_bounds__(256, 2) void nb_march_fold_kernel(MarchArgs a, cons
                 // ---- the colour head's linear part as ONE layer (feature_fc . latent_fc . view_fc folded at pack time, bias:
                 // second block of nb_mlp_latent_bias): one tile per wave, K phase over fc_2's outputs, then over the encodings
                 init_bias<1>(pk + P_LB, wave, hi, acc);
-                layer_s<P_VG, 1, 4, false>(wl, actz, lane_i, ring, acc);
+                layer_s<P_VG, 1, 4, false, true, 30>(wl, actz, lane_i, wave, own, ring, acc, NB_HOOK_TBUF);
                 FOLD_STAMP(10);
                 if (more && tier_next == 0) {
                     const Lvl lv = load_lvl(actz, part);
@@ -1246,7 +1293,7 @@ __global__ __launch_bounds__(256, 2) void nb_march_fold_kernel(MarchArgs a, cons
                 store_halfblock(actz, part >> 1, part & 1, sn, ss, peh);  // the encodings converted behind fc_1
                 __syncthreads();
                 FOLD_STAMP(11);
-                layer_s<P_VP, 1, 2, false>(wl, actz, lane_i, ring, acc);
+                layer_s<P_VP, 1, 2, false, false>(wl, actz, lane_i, wave, own, ring, acc);  // the encodings: every block from LDS
                 FOLD_STAMP(12);
                 FOLD_DUMP(3, 1)
                 // ---- rgb_fc partial sums over this wave's 32 view features
@@ -1426,7 +1473,7 @@ __global__ __launch_bounds__(256) void nb_march_fixup_kernel(MarchArgs a) {
 }
 
 // ---------------------------------------------------------------- weight stream packing
-// input column of the layer phase `ph` held by element e of half-block (b, kh); -1 = zero padding
+// input column of the layer phase `ph` held by element e of half-block (b, kh) of LDS block b; -1 = zero padding
 __device__ __forceinline__ int phase_col(int ph, int b, int kh, int e) {
     if (ph < 3) return col_hidden(32 * b + e, kh);
     return pe_slot_col(2 * b + kh, e);  // the encodings: the owner lane's part
@@ -1483,13 +1530,15 @@ __global__ void nb_pack_fold_kernel(nb_mlp_params p, const float *__restrict__ f
     }
     const int mt = PH_MT[ph], ppb = block_pieces(mt);
     const int rel = piece - p0, b = rel / ppb, r = rel % ppb;
+    // the LDS block whose columns step block b multiplies: wave w walks the published blocks from its own one (layer_s, OWN)
+    const int bl = ph < 3 ? (b + w) & 3 : b;
     unsigned w32[4] = {0u, 0u, 0u, 0u};
     if (r < 4 * mt) {  // A16 of chunk j, tile m
         const int j = r / mt, m = r % mt;
         const int row = (mt == 2 ? 64 * w + 32 * m : 32 * w) + i;
         for (int q = 0; q < 8; q += 2) {
-            const f16x2 hp = {(_Float16)phase_weight(p, f32_blob, ph, row, b, kg, 8 * j + q),
-                              (_Float16)phase_weight(p, f32_blob, ph, row, b, kg, 8 * j + q + 1)};
+            const f16x2 hp = {(_Float16)phase_weight(p, f32_blob, ph, row, bl, kg, 8 * j + q),
+                              (_Float16)phase_weight(p, f32_blob, ph, row, bl, kg, 8 * j + q + 1)};
             w32[q / 2] = __builtin_bit_cast(unsigned, hp);
         }
     } else {  // a cross fragment: k = 0 W_h (multiplies the interleaved remainder operand), k = 1 W_l (natural order) — or the block's hole
@@ -1511,7 +1560,7 @@ __global__ void nb_pack_fold_kernel(nb_mlp_params p, const float *__restrict__ f
             float wv[32], amax = 0.f;
             for (int e = 0; e < 32; ++e) {
                 const int n = k ? e : 16 * (e & 1) + (e >> 1);
-                const float wt = phase_weight(p, f32_blob, ph, row, b, kg, n);
+                const float wt = phase_weight(p, f32_blob, ph, row, bl, kg, n);
                 const float h = (float)(_Float16)wt;
                 wv[e] = k ? wt - h : h;
                 amax = fmaxf(amax, fabsf(wv[e]));

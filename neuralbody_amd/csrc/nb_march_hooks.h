@@ -9,5 +9,6 @@
 #define NB_HOOK_STEP_BEGIN do { } while (0)       // top of a depth step
 #define NB_HOOK_TBUF nullptr                      // where the folded first layer stamps
 #define NB_HOOK_FOLD_FIRST_READ(f) do { } while (0)
+#define NB_HOOK_LAYER_FIRST_READ(u, v) do { } while (0)  // what a layer phase's first MFMA waits for (u, v) has been requested
 #define NB_HOOK_RAW_IS_OUTPUT true                // `raw` carries the decoder output (and not an instrument's records)
 #endif

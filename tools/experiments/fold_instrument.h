@@ -20,12 +20,14 @@
     unsigned *tbuf = (blockIdx.x < 32 && wave == 0 && a.raw) ? reinterpret_cast<unsigned *>(a.raw) + ((size_t)blockIdx.x * S + s) * 32 : nullptr
 #define NB_HOOK_TBUF tbuf
 #define NB_HOOK_FOLD_FIRST_READ(f) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"((f).ah[0]), "+v"((f).bl[1])::"memory")
+#define NB_HOOK_LAYER_FIRST_READ(u, v) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(u), "+v"(v)::"memory")
 #else
 #define FOLD_STAMP(i) do { } while (0)
 #define FOLD_SUB(i) do { } while (0)
 #define NB_HOOK_STEP_BEGIN do { } while (0)
 #define NB_HOOK_TBUF nullptr
 #define NB_HOOK_FOLD_FIRST_READ(f) do { } while (0)
+#define NB_HOOK_LAYER_FIRST_READ(u, v) do { } while (0)
 #endif
 #ifdef FOLD_TAP
 #define FOLD_DUMP(LAYER, MT_)                                                                                             \

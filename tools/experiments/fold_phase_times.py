@@ -41,6 +41,29 @@ sub = [("bias, K list header", 1, 17), ("wait for the first chunk's DMA", 17, 18
 ok = x[:, :, 21] > 0
 print("inside the folded fc_0 (steps on the one-pass path, %.2f chunks on average):" % x[:, :, 21][ok].mean(),
       ", ".join("%s %.0f" % (nm, ((x[:, :, e] - x[:, :, b]) & 0xffffffff)[ok].mean()) for nm, b, e in sub))
+# Around the three publishes, stamps b = 22, 25, 28: b behind the LDS stores, b + 1 behind the barrier that makes them visible, b + 2
+# where the following phase's first MFMA can issue (its bias and, where it reads them from LDS, its first B operands have arrived).
+# "stores -> first MFMA" leaves out the work between the third publish and the colour head (alpha sums, the next step's K list:
+# up to stamp 9).  Where the barrier stands inside the phase (behind its first block) it comes after the first MFMA.
+if (x[:, :, 22:31] != 0).any():
+    step_c = step.mean()
+    dd = lambda e, s0: ((x[:, :, e] - x[:, :, s0]) & 0xffffffff).mean()  # noqa: E731
+    inside = ((x[:, :, 23] - x[:, :, 24]) & 0xffffffff).mean() < (1 << 31)
+    print("\nthe barrier behind the stores stands %s" % ("inside the following phase, behind its first block" if inside else "in the publish"))
+    pubs = (("fc_0 -> fc_1", 2, 3, 22), ("fc_1 -> fc_2", 4, 5, 25), ("fc_2 -> colour head", 7, 9, 28))
+    if inside:  # the phase stores its own block behind its bias reads, multiplies it from registers, then meets the barrier
+        print("\n| publish | convert, barrier | phase begins -> bias there, first MFMA | -> stores issued | first MFMA -> behind the barrier |\n|---|---|---|---|---|")
+        for nm, p0, p1, b in pubs:
+            print("| %s | %.0f | %.0f | %.0f | %.0f |" % (nm, dd(p0 + 1, p0), dd(b + 2, p1), dd(b, b + 2), dd(b + 1, b + 2)))
+    else:
+        print("\n| publish | convert, barrier, stores | stores -> first MFMA of the next phase | share of a step | of it: stores -> behind the barrier |\n|---|---|---|---|---|")
+        wait_sum = 0.0
+        for nm, p0, p1, b in pubs:
+            bar = dd(b + 1, b)
+            w = bar + (dd(b + 2, 9) if b == 28 else dd(b + 2, b + 1))
+            wait_sum += w
+            print("| %s | %.0f | %.0f | %.2f %% | %.0f |" % (nm, dd(b, p0), w, 100 * w / step_c, bar))
+        print("| all three | | %.0f | %.2f %% | |" % (wait_sum, 100 * wait_sum / step_c))
 mf = [1, 3, 5, 9, 11]
 print("MFMA phases %.0f, publishes %.0f, next-step preparation %.0f, barriers (explicit) %.0f" % (
     d[:, mf].sum(1).mean(), d[:, [2, 4, 7]].sum(1).mean(), d[:, [6, 8, 14]].sum(1).mean(), d[:, [0, 13]].sum(1).mean()))
