@@ -701,6 +701,75 @@ int nb_mesh_render(const float *verts, const float *normals, const int32_t *face
                    void *scratch, int64_t scratch_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------------
+ * The extracted mesh cleaned and coloured on device — the reference has neither: every stray blob of density above cfg.mesh_th
+ * becomes a closed surface of its own in the .ply (lib/networks/renderer/if_mesh_renderer.py:46-52, lib/visualizers/
+ * if_nerf_mesh.py:26-34) and the mesh is grey.  The host equivalent of the first three calls is a download,
+ * scipy.sparse.csgraph.connected_components, numpy indexing and an upload.
+ *   Rules of every call: no allocation, no synchronisation, everything on `stream`; integer atomics only, and only where the
+ *   result does not depend on arrival order, so the same input gives the same bits; every loop is counted and no thread waits for
+ *   another; a loop that reaches its limit sets the GIVE-UP WORD, the first int32 of the scratch, and the thread leaves.
+ *   faces dev [T,3] int32; a face with an index outside 0..V-1 is skipped (the rule of nb_mesh_vertex_normals): it connects
+ *   nothing, counts for no component and does not survive the compaction.  0 <= V, T <= 2^31 - 257, else NB_EINVAL.
+ *   scratch dev, 16-byte aligned: nb_mesh_clean_scratch_size(V, T) bytes (0 for refused sizes).  ONE scratch serves the calls of
+ *   one mesh, in this order: components writes the give-up word, select and compact_count read it; compact_count leaves the scan
+ *   positions that compact reads.  A caller with labels or flags of its own zeroes the first 4 bytes instead.
+ * nb_mesh_components — label dev [V] int32 out: the smallest vertex index of v's connected component, two vertices being
+ *   connected when a face uses both; a vertex no face uses is its own component.  Union-find in the scratch under the invariant
+ *   parent[v] <= v: a thread per face unites (a, b) and (a, c), hooking the larger root under the smaller with atomicMin; when
+ *   the atomicMin returns another value than the root it expected, the thread goes on with the pair (returned value, smaller
+ *   root), whose larger member has strictly decreased.  The root of a set is therefore its minimum whatever the order of the
+ *   hooks.  Paths are halved on the way (parent[v] = min(parent[v], grandparent), atomicMin again).  A face spends at most 2^14
+ *   parent reads and hook attempts; if one runs out, the hook launch (idempotent) runs again, up to NB_MESH_HOOK_ROUNDS launches
+ *   in all, every launch after the first returning at once unless the one before it gave up (a word per round in the scratch
+ *   header: nothing is read back).  Then a thread per vertex walks to its root (at most 2^20 steps).  If the last round or a
+ *   walk gave up, the give-up word is 1 and label is NOT written; else it is 0.
+ * nb_mesh_component_select — which components stay.  label as above.  The faces of a component are counted at its label
+ *   (atomicAdd); the largest count wins, a tie going to the smaller label (one 64-bit atomicMax of count << 32 | ~label).
+ *   keep_vertex dev [V] uint8 out: min_fraction = 1: 1 iff v lies in the winning component ("largest": exactly one component);
+ *   0 < min_fraction < 1: 1 iff its component's face count >= max(1, ceil(double(min_fraction) * largest count)).  A component
+ *   without a face is never kept.  stats dev [4] int32 out = {components that have a face, components kept, faces of the
+ *   largest, faces kept}.  With the give-up word set: keep_vertex is not written and stats = {NB_EINTERNAL x 4}.
+ * nb_mesh_compact_count / nb_mesh_compact — the kept part as a mesh of its own.  keep_vertex dev [V] uint8 (any flags, non-zero
+ *   = kept).  A face is kept iff its three indices are in range and its FIRST vertex is kept (with the flags of the call above
+ *   its other two are then kept as well; with other flags an index of a dropped vertex becomes -1).  Two exclusive scans (the
+ *   tile body of csrc/nb_scan_dev.h) number the kept vertices and the kept faces, so both keep their relative order: the
+ *   order contract of nb_marching_cubes holds for the result as a subsequence.  counts dev [2] int32 out = {kept vertices, kept
+ *   faces}, or {NB_EINTERNAL, NB_EINTERNAL} with the give-up word set.  The caller reads these 8 bytes to size the outputs (the
+ *   capacity rule of nb_marching_cubes_emit) and reports NB_EINTERNAL when it finds it there.
+ *   nb_mesh_compact, after nb_mesh_compact_count with the same faces, flags and scratch: verts dev [V,3] fp32 -> verts_out dev
+ *   [vert_cap,3]; faces -> faces_out dev [tri_cap,3] int32, indices renumbered; attr dev [V,3] fp32 or NULL (normals, colours)
+ *   -> attr_out dev [vert_cap,3] or NULL, each row with its vertex.  Rows behind the counts are left alone.  With the give-up
+ *   word set, or a count above its capacity, NOTHING is written (tested on the device; the caller compares the counts it read).
+ * nb_mesh_color_query — what the colour head is asked at every vertex.  verts_idx dev [V,3] fp32 in index units of the padded
+ *   cube (nb_marching_cubes), normals dev [V,3] fp32 (nb_mesh_vertex_normals of the WORLD vertices), step, origin dev [3] fp32,
+ *   pad: wpts dev [V,3] out = ((v (-) pad) (*) step) (+) origin per axis, three fp32 operations, none contracted (RendererMesh's
+ *   world=True); viewdir dev [V,3] out = -n: looking straight at the surface from outside (the table's normals point outwards).
+ *   A zero normal (a vertex no face uses) gives (0, 0, -1).
+ * nb_mesh_color_finish — raw dev [V,4] fp32 (calculate_density_color: rgb logits, sigma) -> rgb_f dev [V,3] fp32 =
+ *   1 (/) (1 (+) expf(-raw)), the sigmoid as nb_composite evaluates it; rgb_u8 dev [V,3] uint8 = rint(255 (*) rgb_f), half to
+ *   even, clamped to 0..255 (a NaN gives 0).
+ * nb_mesh_render_attr — nb_mesh_render with the vertex colour READ from attr dev [V,3] fp32 instead of computed as
+ *   0.5 (*) (N . n) (+) 0.5: the same cameras, snapped coverage, 64-bit key and interpolation expression (one triangle walker,
+ *   one resolve kernel in two instantiations).  Fed that expression as attr, it returns nb_mesh_render's bits.  Same scratch. */
+#define NB_EINTERNAL (-4) /* a counted device loop gave up (written into device outputs; see the mesh clean-up) */
+#define NB_MESH_HOOK_ROUNDS 4
+int64_t nb_mesh_clean_scratch_size(int32_t n_verts, int32_t n_faces);
+int nb_mesh_components(const int32_t *faces, int32_t n_verts, int32_t n_faces, int32_t *label, void *scratch, void *stream);
+int nb_mesh_component_select(const int32_t *label, const int32_t *faces, int32_t n_verts, int32_t n_faces, float min_fraction,
+                             uint8_t *keep_vertex, int32_t *stats, void *scratch, void *stream);
+int nb_mesh_compact_count(const int32_t *faces, const uint8_t *keep_vertex, int32_t n_verts, int32_t n_faces, int32_t *counts,
+                          void *scratch, void *stream);
+int nb_mesh_compact(const float *verts, const int32_t *faces, const float *attr, int32_t n_verts, int32_t n_faces,
+                    float *verts_out, int32_t *faces_out, float *attr_out, int32_t vert_cap, int32_t tri_cap, void *scratch,
+                    void *stream);
+int nb_mesh_color_query(const float *verts_idx, const float *normals, const float *step, const float *origin, float pad,
+                        int32_t n_verts, float *wpts, float *viewdir, void *stream);
+int nb_mesh_color_finish(const float *raw, int32_t n_verts, float *rgb_f, uint8_t *rgb_u8, void *stream);
+int nb_mesh_render_attr(const float *verts, const float *attr, const int32_t *faces, int32_t n_verts, int32_t n_faces,
+                        const float *cams, int32_t n_views, int32_t H, int32_t W, float *rgb, int32_t *face_id, float *depth,
+                        void *scratch, int64_t scratch_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------------
  * A photographed frame on device — replaces the OpenCV calls between the image files and the kernels above:
  * lib/datasets/light_stage/multi_view_dataset.py:58-64 (get_mask: cv2.erode, cv2.dilate, the border band), :129-142 (cv2.undistort
  * of the float32 image and the uint8 mask, cv2.resize INTER_AREA / INTER_NEAREST by cfg.ratio, the background fill) and

@@ -19,6 +19,7 @@ PAD_MODES = {"zju": 0, "big_box": 1, "snapshot": 2}  # NB_PAD_ZJU, NB_PAD_BIG_BO
 SMPL_JOINTS, SMPL_POSE_BASIS, SMPL_BETAS, SMPL_PARAMS, SMPL_WS_FLOATS = 24, 207, 10, 88, 512  # NB_SMPL_*
 CAM_DOUBLES = 12  # NB_CAM_DOUBLES
 FILL_MODES = {None: 0, "black": 1, "white": 2}  # NB_FILL_NONE, NB_FILL_BLACK, NB_FILL_WHITE
+EINTERNAL = -4  # NB_EINTERNAL: what a device output holds when a counted loop gave up
 
 
 def ill_scratch_bytes(cap):
@@ -141,6 +142,14 @@ SIGNATURES = {
     "nb_mesh_vertex_normals": (C.c_int, [_P, _P, _I32, _I32, _P, _P, _P]),
     "nb_mesh_render_scratch_size": (_I64, [_I32, _I32, _I32, _I32]),
     "nb_mesh_render": (C.c_int, [_P, _P, _P, _I32, _I32, _P, _I32, _I32, _I32, _P, _P, _P, _P, _I64, _P]),
+    "nb_mesh_clean_scratch_size": (_I64, [_I32, _I32]),
+    "nb_mesh_components": (C.c_int, [_P, _I32, _I32, _P, _P, _P]),
+    "nb_mesh_component_select": (C.c_int, [_P, _P, _I32, _I32, C.c_float, _P, _P, _P, _P]),
+    "nb_mesh_compact_count": (C.c_int, [_P, _P, _I32, _I32, _P, _P, _P]),
+    "nb_mesh_compact": (C.c_int, [_P, _P, _P, _I32, _I32, _P, _P, _P, _I32, _I32, _P, _P]),
+    "nb_mesh_color_query": (C.c_int, [_P, _P, _P, _P, C.c_float, _I32, _P, _P, _P]),
+    "nb_mesh_color_finish": (C.c_int, [_P, _I32, _P, _P, _P]),
+    "nb_mesh_render_attr": (C.c_int, [_P, _P, _P, _I32, _I32, _P, _I32, _I32, _I32, _P, _P, _P, _P, _I64, _P]),
     "nb_mask_band": (C.c_int, [_P, _I32, _I32, _I32, _I32, _P, _P]),
     "nb_image_undistort": (C.c_int, [_P, _P, C.POINTER(C.c_double), _I32, _I32, _I32, _I32, C.c_int, _P, _P, _P]),
 }

@@ -203,7 +203,9 @@ __global__ __launch_bounds__(256) void raster_large_kernel(RasterJob job, unsign
     nbraster::large_pass(job, n, count, large);
 }
 
-// One thread per pixel: the winner's sample again, by the functions that made the key, then its colour.
+// One thread per pixel: the winner's sample again, by the functions that made the key, then its colour.  ATTR: `normals` holds the
+// vertex colours themselves (nb_mesh_render_attr) instead of the normals they are computed from.
+template <bool ATTR>
 __global__ __launch_bounds__(256) void resolve_kernel(const float *__restrict__ verts, const float *__restrict__ normals,
                                                       const int *__restrict__ faces, const float *__restrict__ cams, int n_px, int T,
                                                       int V, int H, int W, const unsigned long long *__restrict__ keys,
@@ -220,11 +222,15 @@ __global__ __launch_bounds__(256) void resolve_kernel(const float *__restrict__ 
     if (key != EMPTY && (unsigned)tri < (unsigned)T && tri_setup(tri, faces, verts, V, cam, H, W, t) && x >= t.x0 && x <= t.x1 &&
         y >= t.y0 && y <= t.y1 && sample(t, x, y, l1, l2, d)) {
         id = tri;
-        float col[3][3];  // [vertex][channel]: 0.5 n' + 0.5, n' the normal through the view's rotation
+        float col[3][3];  // [vertex][channel]: 0.5 n' + 0.5, n' the normal through the view's rotation; or the attribute as it is
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
             const float *__restrict__ nv = normals + 3 * (size_t)t.idx[k];
             const float nx = nv[0], ny = nv[1], nz = nv[2];
+            if (ATTR) {
+                col[k][0] = nx, col[k][1] = ny, col[k][2] = nz;
+                continue;
+            }
 #pragma unroll
             for (int i = 0; i < 3; ++i)
                 col[k][i] = add(mul(0.5f, dot3(cam[12 + 3 * i], cam[12 + 3 * i + 1], cam[12 + 3 * i + 2], nx, ny, nz)), 0.5f);
@@ -263,19 +269,23 @@ extern "C" int64_t nb_mesh_render_scratch_size(int32_t n_views, int32_t H, int32
     return carve(nullptr, n_views, H, W, T).total_bytes;
 }
 
-extern "C" int nb_mesh_render(const float *verts, const float *normals, const int32_t *faces, int32_t V, int32_t T, const float *cams,
-                              int32_t n_views, int32_t H, int32_t W, float *rgb, int32_t *face_id, float *depth, void *scratch,
-                              int64_t scratch_bytes, void *stream) {
-    NB_REQUIRE(cams && rgb && scratch, "nb_mesh_render: NULL pointer");
-    NB_REQUIRE(V >= 0 && T >= 0 && (T == 0 || (verts && normals && faces)), "nb_mesh_render: V = %d, T = %d with a NULL mesh pointer",
+namespace {
+
+// both entries: `what` names the caller in the refusals, ATTR says what `normals` holds (resolve_kernel)
+template <bool ATTR>
+int render(const char *what, const float *verts, const float *normals, const int32_t *faces, int32_t V, int32_t T, const float *cams,
+           int32_t n_views, int32_t H, int32_t W, float *rgb, int32_t *face_id, float *depth, void *scratch, int64_t scratch_bytes,
+           void *stream) {
+    NB_REQUIRE(cams && rgb && scratch, "%s: NULL pointer", what);
+    NB_REQUIRE(V >= 0 && T >= 0 && (T == 0 || (verts && normals && faces)), "%s: V = %d, T = %d with a NULL mesh pointer", what,
                V, T);
     const Scratch s = carve(scratch, n_views, H, W, T);
     NB_REQUIRE(s.total_bytes > 0,
-               "nb_mesh_render: n_views = %d (>= 1), H = %d, W = %d (1..32768), T = %d (>= 0), n_views H W and n_views T below 2^31 - 256",
+               "%s: n_views = %d (>= 1), H = %d, W = %d (1..32768), T = %d (>= 0), n_views H W and n_views T below 2^31 - 256", what,
                n_views, H, W, T);
-    NB_REQUIRE(scratch_bytes >= s.total_bytes, "nb_mesh_render: scratch holds %lld bytes, %lld needed", (long long)scratch_bytes,
+    NB_REQUIRE(scratch_bytes >= s.total_bytes, "%s: scratch holds %lld bytes, %lld needed", what, (long long)scratch_bytes,
                s.total_bytes);
-    NB_REQUIRE(((uintptr_t)scratch & 15) == 0, "nb_mesh_render: scratch must be 16-byte aligned");
+    NB_REQUIRE(((uintptr_t)scratch & 15) == 0, "%s: scratch must be 16-byte aligned", what);
     hipStream_t st = (hipStream_t)stream;
     const int n_tri = n_views * T, n_px = n_views * H * W;
     NB_HIP(hipMemsetAsync(s.hdr, 0, HDR_BYTES, st));                       // the large-triangle count
@@ -287,8 +297,24 @@ extern "C" int nb_mesh_render(const float *verts, const float *normals, const in
         hipLaunchKernelGGL(raster_large_kernel, dim3(nbraster::LARGE_BLOCKS), dim3(256), 0, st, job, s.keys, n_tri, s.hdr, s.large);
         NB_CHECK_LAUNCH("nb_mesh_render (large triangles)");
     }
-    hipLaunchKernelGGL(resolve_kernel, dim3(nb_ceil_div(n_px, 256)), dim3(256), 0, st, verts, normals, faces, cams, n_px, T, V, H, W,
+    hipLaunchKernelGGL(resolve_kernel<ATTR>, dim3(nb_ceil_div(n_px, 256)), dim3(256), 0, st, verts, normals, faces, cams, n_px, T, V, H, W,
                        s.keys, rgb, face_id, depth);
     NB_CHECK_LAUNCH("nb_mesh_render (resolve)");
     return NB_OK;
+}
+
+}  // namespace
+
+extern "C" int nb_mesh_render(const float *verts, const float *normals, const int32_t *faces, int32_t V, int32_t T, const float *cams,
+                              int32_t n_views, int32_t H, int32_t W, float *rgb, int32_t *face_id, float *depth, void *scratch,
+                              int64_t scratch_bytes, void *stream) {
+    return render<false>("nb_mesh_render", verts, normals, faces, V, T, cams, n_views, H, W, rgb, face_id, depth, scratch, scratch_bytes,
+                         stream);
+}
+
+extern "C" int nb_mesh_render_attr(const float *verts, const float *attr, const int32_t *faces, int32_t V, int32_t T, const float *cams,
+                                   int32_t n_views, int32_t H, int32_t W, float *rgb, int32_t *face_id, float *depth, void *scratch,
+                                   int64_t scratch_bytes, void *stream) {
+    return render<true>("nb_mesh_render_attr", verts, attr, faces, V, T, cams, n_views, H, W, rgb, face_id, depth, scratch, scratch_bytes,
+                        stream);
 }

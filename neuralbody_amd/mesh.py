@@ -1,27 +1,45 @@
 """`TriMesh` — what RendererMesh.render returns as `mesh` where trimesh is not installed: the vertices, the faces and the one method
-the reference's mesh visualizer calls on it (lib/visualizers/if_nerf_mesh.py:26-34, `mesh.export(path)`)."""
+the reference's mesh visualizer calls on it (lib/visualizers/if_nerf_mesh.py:26-34, `mesh.export(path)`); optionally a colour per
+vertex (cfg.mesh_color), which the reference's meshes never have."""
 import numpy as np
 
 
 class TriMesh:
-    def __init__(self, vertices, faces):
+    def __init__(self, vertices, faces, vertex_colors=None):
         self.vertices = np.ascontiguousarray(vertices, dtype=np.float64).reshape(-1, 3)
         self.faces = np.ascontiguousarray(faces, dtype=np.int64).reshape(-1, 3)
+        self.vertex_colors = None  # uint8 [V,3] RGB, or None: a mesh without colours
+        if vertex_colors is not None:
+            colors = np.asarray(vertex_colors)
+            if colors.dtype != np.uint8 or colors.shape != (len(self.vertices), 3):
+                raise ValueError("vertex_colors must be uint8 [%d,3], got %s %s" % (len(self.vertices), colors.dtype, colors.shape))
+            self.vertex_colors = np.ascontiguousarray(colors)
 
     def export(self, path):
-        """Binary little-endian PLY: float32 vertices, triangles as `list uchar int` (what trimesh writes for a `.ply` path)."""
+        r"""Binary little-endian PLY: float32 vertices, triangles as `list uchar int` (what trimesh writes for a `.ply` path); with
+        vertex_colors, `property uchar red / green / blue` behind x y z (what trimesh writes for a coloured mesh, without alpha).
+        Without colours the header is
+            "ply\nformat binary_little_endian 1.0\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\n"
+            "element face %d\nproperty list uchar int vertex_indices\nend_header\n" % (V, T)
+        followed by V x 3 little-endian float32 and T records of (uchar 3, 3 little-endian int32)."""
         path = str(path)
         if not path.lower().endswith(".ply"):
             raise ValueError("TriMesh.export writes PLY only (got %r); install trimesh for other formats" % path)
         nv, nf = len(self.vertices), len(self.faces)
-        header = ("ply\nformat binary_little_endian 1.0\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\n"
-                  "element face %d\nproperty list uchar int vertex_indices\nend_header\n" % (nv, nf))
+        colors = "" if self.vertex_colors is None else "property uchar red\nproperty uchar green\nproperty uchar blue\n"
+        header = ("ply\nformat binary_little_endian 1.0\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\n%s"
+                  "element face %d\nproperty list uchar int vertex_indices\nend_header\n" % (nv, colors, nf))
         faces = np.empty(nf, dtype=[("n", "u1"), ("v", "<i4", (3,))])
         faces["n"] = 3
         faces["v"] = self.faces
         with open(path, "wb") as f:
             f.write(header.encode("ascii"))
-            f.write(self.vertices.astype("<f4").tobytes())
+            if self.vertex_colors is None:
+                f.write(self.vertices.astype("<f4").tobytes())
+            else:
+                verts = np.empty(nv, dtype=[("p", "<f4", (3,)), ("c", "u1", (3,))])
+                verts["p"], verts["c"] = self.vertices, self.vertex_colors
+                f.write(verts.tobytes())
             f.write(faces.tobytes())
         return path
 
@@ -32,7 +50,8 @@ class TriMesh:
     @classmethod
     def load_ply(cls, path):
         """Reads what `export` and trimesh write: binary little-endian PLY, a vertex element with float or double x / y / z
-        (further scalar properties are skipped), then a face element of `list uchar int|uint` triangles.  Anything else is
+        (uchar red / green / blue, when all three are there, come back as vertex_colors; further scalar properties are skipped), then
+        a face element of `list uchar int|uint` triangles.  Anything else is
         refused with what was found."""
         with open(str(path), "rb") as f:
             data = f.read()
@@ -71,4 +90,7 @@ class TriMesh:
         faces = np.frombuffer(data, fdtype, nf, body + nv * vdtype.itemsize)
         if nf and (faces["n"] != 3).any():
             raise ValueError("%s: only triangles are read, found a face of %d vertices" % (path, int(faces["n"][faces["n"] != 3][0])))
-        return cls(np.stack([verts["x"], verts["y"], verts["z"]], 1), faces["v"])
+        colors = None
+        if all(k in vdtype.names and vdtype[k] == np.uint8 for k in ("red", "green", "blue")):
+            colors = np.stack([verts["red"], verts["green"], verts["blue"]], 1)
+        return cls(np.stack([verts["x"], verts["y"], verts["z"]], 1), faces["v"], colors)

@@ -88,7 +88,9 @@ def _jpeg_writer():
 
 
 class MeshTurntable:
-    """render(vertices, triangles) -> device float32 [n_views,H,W,3] RGB in 0..1; save(images, directory) -> `%d.jpg`."""
+    """render(vertices, triangles) -> device float32 [n_views,H,W,3] RGB in 0..1; save(images, directory) -> `%d.jpg`.
+    render(..., colors=...) draws the mesh in its vertex colours instead of the normal shading: the same cameras, coverage and
+    depth test (ops.mesh_render_attr)."""
 
     def __init__(self, H=512, W=512, dataset="zju_mocap", views_per_call=16, device="cuda:0", n_views=91, step_deg=4.0,
                  ortho_ratio=1.2):
@@ -116,16 +118,32 @@ class MeshTurntable:
         cams = turntable_cams(box[0], box[1], self.H, self.W, self.dataset, self.n_views, self.step_deg, self.ortho_ratio)
         return torch.from_numpy(cams.astype(np.float32)).to(vertices.device)
 
-    def render(self, vertices, triangles=None, normals=None):
+    def _colors(self, colors, mesh, V):
+        """float32 [V,3] in 0..1 on the device from `colors`: True (the host mesh's own vertex_colors), a uint8 array or tensor
+        (divided by 255) or a float one (taken as it is: RendererMesh.extract_mesh's rgb_f)."""
+        if colors is True:
+            colors = getattr(mesh, "vertex_colors", None)
+            if colors is None:
+                raise ValueError("colors=True needs a mesh that carries vertex_colors")
+        c = torch.as_tensor(np.asarray(colors) if not isinstance(colors, torch.Tensor) else colors).detach().to(self.device)
+        c = c.float() / 255.0 if c.dtype == torch.uint8 else c.float()
+        if tuple(c.shape) != (V, 3):
+            raise ValueError("colors has shape %s, the mesh has %d vertices" % (tuple(c.shape), V))
+        return c.contiguous()
+
+    def render(self, vertices, triangles=None, normals=None, colors=False):
         v, t = self._mesh(vertices, triangles)
-        cams = self.cams(v)
-        if normals is None:
+        draw = ops.mesh_render
+        if colors is not False and colors is not None:
+            draw, normals = ops.mesh_render_attr, self._colors(colors, vertices, v.shape[0])
+        elif normals is None:
             normals = ops.mesh_vertex_normals(v, t)
+        cams = self.cams(v)
         n = min(self.views_per_call, self.n_views)
         scratch = ops.mesh_render_scratch(n, self.H, self.W, t.shape[0], v.device)  # the keys stay at views_per_call H W 8 bytes
         out = torch.empty((self.n_views, self.H, self.W, 3), dtype=torch.float32, device=v.device)
         for k in range(0, self.n_views, n):
-            ops.mesh_render(v, normals, t, cams[k:k + n], self.H, self.W, out=out[k:k + n], scratch=scratch)
+            draw(v, normals, t, cams[k:k + n], self.H, self.W, out=out[k:k + n], scratch=scratch)
         return out
 
     def save(self, images, directory):

@@ -1287,7 +1287,7 @@ def mesh_render_scratch(n_views, H, W, T, device):
 
 
 def mesh_render(vertices, normals, triangles, cams, H, W, out=None, want_face_id=False, want_depth=False, scratch=None,
-                face_id=None, depth=None):
+                face_id=None, depth=None, _entry="nb_mesh_render"):
     """nb_mesh_render: vertices, normals device fp32 [V,3], triangles device int32 [T,3], cams device fp32 [n,24] (per view the
     3 x 4 affine to (x_px, y_px, depth) | the 3 x 3 rotation of the normals | 3 of padding: mesh_render.turntable_cams) ->
     rgb device fp32 [n,H,W,3], white where nothing is drawn; with want_face_id and / or want_depth a tuple (rgb[, face_id int32
@@ -1320,10 +1320,212 @@ def mesh_render(vertices, normals, triangles, cams, H, W, out=None, want_face_id
     if depth is not None:
         _req(depth, torch.float32, (n, H, W), "depth")
     with torch.cuda.device(dev):
-        check(_lib.lib().nb_mesh_render(ptr(vertices), ptr(normals), ptr(triangles), V, T, ptr(cams), n, H, W, ptr(out), ptr(face_id),
-                                        ptr(depth), ptr(scratch), int(scratch.numel()), _stream()), "nb_mesh_render")
+        check(getattr(_lib.lib(), _entry)(ptr(vertices), ptr(normals), ptr(triangles), V, T, ptr(cams), n, H, W, ptr(out), ptr(face_id),
+                                          ptr(depth), ptr(scratch), int(scratch.numel()), _stream()), _entry)
     extra = tuple(t for t in (face_id, depth) if t is not None)
     return (out,) + extra if extra else out
+
+
+def mesh_render_attr(vertices, attr, triangles, cams, H, W, out=None, want_face_id=False, want_depth=False, scratch=None,
+                     face_id=None, depth=None):
+    """nb_mesh_render_attr: mesh_render with the vertex colours read from `attr`, device fp32 [V,3] (mesh_vertex_colors' rgb_f),
+    instead of computed from normals; arguments, outputs and scratch as mesh_render.  Nothing is read back."""
+    return mesh_render(vertices, attr, triangles, cams, H, W, out=out, want_face_id=want_face_id, want_depth=want_depth,
+                       scratch=scratch, face_id=face_id, depth=depth, _entry="nb_mesh_render_attr")
+
+
+# ------------------------------------------------------------------------------------------- the extracted mesh cleaned and coloured
+MESH_HOOK_ROUNDS = 4  # NB_MESH_HOOK_ROUNDS
+
+
+def _mesh(vertices, triangles, V=None):
+    """(V, T, device) of a face list and, when given, the vertices it indexes."""
+    _req(triangles, torch.int32, (None, 3), "triangles")
+    if vertices is not None:
+        _req(vertices, torch.float32, (None, 3), "vertices")
+        if vertices.device != triangles.device:
+            raise ValueError("vertices and triangles live on different devices")
+        V = vertices.shape[0]
+    return int(V), int(triangles.shape[0]), triangles.device
+
+
+def mesh_clean_scratch(V, T, device):
+    """The one scratch of mesh_components, mesh_component_select and mesh_compact for a mesh of V vertices and T triangles."""
+    return _raster_scratch("nb_mesh_clean_scratch_size", (V, T), device, "no mesh clean-up for V = %d, T = %d (0..2^31 - 257)")
+
+
+def _clean_scratch(scratch, V, T, dev):
+    if scratch is None:
+        scratch = mesh_clean_scratch(V, T, dev)
+        scratch[:4].zero_()  # the give-up word, for a caller that starts behind mesh_components
+    return _req(scratch, torch.uint8, (None,), "scratch")
+
+
+def mesh_give_up(scratch):
+    """The give-up word of a clean-up scratch as a device int32 [1] view: 0, or 1 when mesh_components could not finish."""
+    return _req(scratch, torch.uint8, (None,), "scratch")[:4].view(torch.int32)
+
+
+def mesh_components(triangles, n_vertices, out=None, scratch=None):
+    """nb_mesh_components: triangles device int32 [T,3] over n_vertices vertices (a face with an index outside 0..V-1 is skipped)
+    -> label device int32 [V]: the smallest vertex index of each vertex's connected component; a vertex no face uses is its own.
+    scratch: mesh_clean_scratch(V, T, device) (allocated when None); pass the same one on to mesh_component_select and
+    mesh_compact, which read its give-up word.  Nothing is read back."""
+    V, T, dev = _mesh(None, triangles, n_vertices)
+    scratch = _clean_scratch(scratch, V, T, dev)
+    if out is None:
+        out = torch.empty(V, dtype=torch.int32, device=dev)
+    _req(out, torch.int32, (V,), "out")
+    with torch.cuda.device(dev):
+        check(_lib.lib().nb_mesh_components(ptr(triangles), V, T, ptr(out), ptr(scratch), _stream()), "nb_mesh_components")
+    return out
+
+
+def mesh_component_select(label, triangles, components="largest", keep=None, stats=None, scratch=None):
+    """nb_mesh_component_select: label device int32 [V] (mesh_components), triangles device int32 [T,3]; components "largest"
+    (the component of most faces, a tie going to the smaller label) or a float f in (0, 1] (every component of at least
+    ceil(f * largest) faces; 1.0 is "largest") -> (keep_vertex device uint8 [V], stats device int32 [4] = {components that
+    have a face, components kept, faces of the largest, faces kept}).  A component without a face is never kept.  Nothing is
+    read back."""
+    _req(label, torch.int32, (None,), "label")
+    V, T, dev = _mesh(None, triangles, label.shape[0])
+    if label.device != dev:
+        raise ValueError("label and triangles live on different devices")
+    fraction = mesh_components_fraction(components)
+    if fraction is None:
+        raise ValueError("components = 'all' selects nothing: skip the call")
+    scratch = _clean_scratch(scratch, V, T, dev)
+    if keep is None:
+        keep = torch.empty(V, dtype=torch.uint8, device=dev)
+    if stats is None:
+        stats = torch.empty(4, dtype=torch.int32, device=dev)
+    _req(keep, torch.uint8, (V,), "keep")
+    _req(stats, torch.int32, (4,), "stats")
+    with torch.cuda.device(dev):
+        check(_lib.lib().nb_mesh_component_select(ptr(label), ptr(triangles), V, T, fraction, ptr(keep), ptr(stats), ptr(scratch),
+                                                  _stream()), "nb_mesh_component_select")
+    return keep, stats
+
+
+def mesh_components_fraction(components):
+    """The `components` argument of the mesh pass as nb_mesh_component_select's min_fraction: "all" / None / False -> None (no
+    clean-up), "largest" -> 1.0, a number in (0, 1] -> itself; anything else is a ValueError."""
+    if components is None or components is False or components == "all":
+        return None
+    if components == "largest":
+        return 1.0
+    if isinstance(components, (int, float)) and not isinstance(components, bool) and 0.0 < float(components) <= 1.0:
+        return float(components)
+    raise ValueError("components must be 'all', 'largest' or a number in (0, 1], got %r" % (components,))
+
+
+def mesh_compact_count(triangles, keep, scratch, counts=None):
+    """nb_mesh_compact_count: the two scans of mesh_compact -> counts, a [2] int32 device tensor {kept vertices, kept triangles};
+    nothing is read back."""
+    _req(keep, torch.uint8, (None,), "keep")
+    V, T, dev = _mesh(None, triangles, keep.shape[0])
+    if keep.device != dev:
+        raise ValueError("keep and triangles live on different devices")
+    _req(scratch, torch.uint8, (None,), "scratch")
+    if counts is None:
+        counts = torch.empty(2, dtype=torch.int32, device=dev)
+    _req(counts, torch.int32, (2,), "counts")
+    with torch.cuda.device(dev):
+        check(_lib.lib().nb_mesh_compact_count(ptr(triangles), ptr(keep), V, T, ptr(counts), ptr(scratch), _stream()),
+              "nb_mesh_compact_count")
+    return counts
+
+
+def _kept_counts(counts):
+    """The ONE 8-byte read of a compaction: (kept vertices, kept triangles) on the host; NbError for NB_EINTERNAL."""
+    n_vert, n_tri = (int(v) for v in counts.tolist())
+    if n_vert == _lib.EINTERNAL or n_tri == _lib.EINTERNAL:
+        raise NbError("nb_mesh_components failed (%d, NB_EINTERNAL): a hook or a walk to the root was still unfinished after %d "
+                      "rounds; no label was written" % (_lib.EINTERNAL, MESH_HOOK_ROUNDS))
+    return n_vert, n_tri
+
+
+def mesh_compact_emit(vertices, triangles, scratch, counts, vertices_out, triangles_out, attr=None, attr_out=None):
+    """nb_mesh_compact into caller-owned buffers (vertices_out [Vcap,3] float32, triangles_out [Tcap,3] int32, attr_out [Vcap,3]
+    float32 iff attr is given) after mesh_compact_count on the same triangles, flags and scratch.  counts: that call's result,
+    as the device tensor (read here, the one 8-byte read) or as the pair of ints already read.  Raises NbError, with the buffers
+    untouched, when they are too small."""
+    V, T, dev = _mesh(vertices, triangles)
+    _req(scratch, torch.uint8, (None,), "scratch")
+    _req(vertices_out, torch.float32, (None, 3), "vertices_out")
+    _req(triangles_out, torch.int32, (None, 3), "triangles_out")
+    if (attr is None) != (attr_out is None):
+        raise ValueError("attr and attr_out go together")
+    if attr is not None:
+        _req(attr, torch.float32, (V, 3), "attr")
+        _req(attr_out, torch.float32, (vertices_out.shape[0], 3), "attr_out")
+    n_vert, n_tri = _kept_counts(counts) if isinstance(counts, torch.Tensor) else (int(counts[0]), int(counts[1]))
+    if n_vert > vertices_out.shape[0] or n_tri > triangles_out.shape[0]:
+        raise NbError("nb_mesh_compact failed (-1): the kept mesh has %d vertices and %d triangles, the buffers hold %d and %d" % (
+            n_vert, n_tri, vertices_out.shape[0], triangles_out.shape[0]))
+    with torch.cuda.device(dev):
+        check(_lib.lib().nb_mesh_compact(ptr(vertices), ptr(triangles), ptr(attr), V, T, ptr(vertices_out), ptr(triangles_out),
+                                         ptr(attr_out), vertices_out.shape[0], triangles_out.shape[0], ptr(scratch), _stream()),
+              "nb_mesh_compact")
+    return (vertices_out, triangles_out) if attr is None else (vertices_out, triangles_out, attr_out)
+
+
+def mesh_compact(vertices, triangles, keep, attr=None, scratch=None):
+    """The kept part of a mesh as a mesh of its own: vertices device fp32 [V,3], triangles device int32 [T,3], keep device uint8
+    [V] (mesh_component_select) -> (vertices [V',3], triangles [T',3][, attr [V',3]]), device tensors of the exact size; kept
+    vertices and triangles keep their relative order, the indices are renumbered, an optional per-vertex fp32 [V,3] attribute
+    (normals, colours) travels with its vertex.  A triangle is kept iff its indices are in range and its first vertex is kept.
+    Count, ONE host read of the two counts, allocate, emit."""
+    V, T, dev = _mesh(vertices, triangles)
+    _req(keep, torch.uint8, (V,), "keep")
+    scratch = _clean_scratch(scratch, V, T, dev)
+    n_vert, n_tri = _kept_counts(mesh_compact_count(triangles, keep, scratch))
+    vertices_out = torch.empty((n_vert, 3), dtype=torch.float32, device=dev)
+    triangles_out = torch.empty((n_tri, 3), dtype=torch.int32, device=dev)
+    attr_out = None if attr is None else torch.empty((n_vert, 3), dtype=torch.float32, device=dev)
+    return mesh_compact_emit(vertices, triangles, scratch, (n_vert, n_tri), vertices_out, triangles_out, attr, attr_out)
+
+
+def mesh_color_query(vertices_idx, normals, step, origin, pad):
+    """nb_mesh_color_query: vertices_idx device fp32 [V,3] (index units of the padded cube), normals device fp32 [V,3], step and
+    origin device fp32 [3], pad a number -> (wpts [V,3] = (v - pad) * step + origin, three fp32 operations per axis; viewdir [V,3]
+    = -normal, (0, 0, -1) for a zero normal).  Nothing is read back."""
+    _req(vertices_idx, torch.float32, (None, 3), "vertices_idx")
+    V, dev = int(vertices_idx.shape[0]), vertices_idx.device
+    _req(normals, torch.float32, (V, 3), "normals")
+    _req(step, torch.float32, (3,), "step")
+    _req(origin, torch.float32, (3,), "origin")
+    if normals.device != dev or step.device != dev or origin.device != dev:
+        raise ValueError("vertices_idx, normals, step and origin live on different devices")
+    wpts, viewdir = torch.empty_like(vertices_idx), torch.empty_like(vertices_idx)
+    with torch.cuda.device(dev):
+        check(_lib.lib().nb_mesh_color_query(ptr(vertices_idx), ptr(normals), ptr(step), ptr(origin), float(pad), V, ptr(wpts),
+                                             ptr(viewdir), _stream()), "nb_mesh_color_query")
+    return wpts, viewdir
+
+
+def mesh_color_finish(raw):
+    """nb_mesh_color_finish: raw device fp32 [V,4] (calculate_density_color) -> (rgb_f fp32 [V,3] = sigmoid of the three logits,
+    rgb_u8 uint8 [V,3] = rint(255 rgb_f), half to even).  Nothing is read back."""
+    _req(raw, torch.float32, (None, 4), "raw")
+    V, dev = int(raw.shape[0]), raw.device
+    rgb_f = torch.empty((V, 3), dtype=torch.float32, device=dev)
+    rgb_u8 = torch.empty((V, 3), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        check(_lib.lib().nb_mesh_color_finish(ptr(raw), V, ptr(rgb_f), ptr(rgb_u8), _stream()), "nb_mesh_color_finish")
+    return rgb_f, rgb_u8
+
+
+def mesh_vertex_colors(vertices_idx, normals, step, origin, pad, decode):
+    """The colour of every vertex from the colour head: mesh_color_query, ONE call of `decode(wpts [1,V,3], viewdir [1,V,3]) ->
+    raw [1,V,4]` (Network.calculate_density_color bound to the frame's feature volumes), mesh_color_finish -> (rgb_f fp32 [V,3],
+    rgb_u8 uint8 [V,3], wpts, viewdir).  A mesh without vertices asks nothing."""
+    wpts, viewdir = mesh_color_query(vertices_idx, normals, step, origin, pad)
+    if vertices_idx.shape[0] == 0:
+        raw = torch.empty((0, 4), dtype=torch.float32, device=vertices_idx.device)
+    else:
+        raw = decode(wpts[None], viewdir[None]).reshape(-1, 4).float().contiguous()
+    return mesh_color_finish(raw) + (wpts, viewdir)
 
 
 # ------------------------------------------------------------------------------------------- a photographed frame

@@ -24,6 +24,7 @@ class _LiveCfg:
     result_dir = property(lambda self: cfg.result_dir)
     mesh_render = property(lambda self: bool(getattr(cfg, "mesh_render", False)))  # not a reference key: off unless set
     mesh_render_dataset = property(lambda self: str(getattr(cfg, "mesh_render_dataset", "zju_mocap")))
+    mesh_render_color = property(lambda self: bool(getattr(cfg, "mesh_render_color", False)))  # likewise; needs mesh_color
     mesh_render_size = property(lambda self: tuple(int(v) for v in getattr(cfg, "mesh_render_size", (512, 512))))
 
 

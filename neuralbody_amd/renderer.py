@@ -9,6 +9,8 @@ The overridable pieces the reference's subclasses rely on are kept with the same
 get_density_color, get_pixel_value.  get_pixel_value (points decoded through the Network API, then
 nb_composite) is what a subclass that culls samples would call; render() itself uses the fused path.
 """
+import collections
+
 import torch
 
 from . import ops
@@ -19,7 +21,7 @@ class RenderConfig:
     """The cfg keys the hot path reads."""
 
     def __init__(self, N_samples=64, perturb=0.0, raw_noise_std=0.0, white_bkgd=False, H=None, W=None, mesh_th=50.0,
-                 mesh_backend="auto"):
+                 mesh_backend="auto", mesh_components="all", mesh_color=False):
         # H, W (optional): image size of the view the rays come from (cfg.H * cfg.ratio in the reference); when
         # batch['mask_at_box'] covers H*W pixels, rays are marched in 8x8 pixel tiles
         self.H, self.W = H, W
@@ -31,6 +33,14 @@ class RenderConfig:
         # RendererMesh.render: "auto" = PyMCubes on the host when it imports, else marching cubes on the device; "device" = always
         # on the device (not a reference key)
         self.mesh_backend = str(mesh_backend)
+        # RendererMesh.render (not reference keys, off unless set): which connected components of the mesh stay ("all", "largest"
+        # or a fraction in (0, 1] of the largest one's faces) and whether every vertex gets a colour from the colour head
+        self.mesh_components = mesh_components
+        self.mesh_color = bool(mesh_color)
+
+
+class ColoredMesh(collections.namedtuple("ColoredMesh", "vertices triangles rgb_f rgb_u8 wpts viewdir normals")):
+    """RendererMesh.extract_mesh(colors=True): device tensors; the first two are what it returns without colours."""
 
 
 class SpInput(dict):
@@ -437,7 +447,8 @@ class RendererMesh(Renderer):
     lattice point flagged `inside`) runs on HIP in ONE nb_decode_points launch (the reference chunks 131 072 points per
     call, :37).  Marching cubes (:46-52) runs on the device too (`extract_mesh`: nb_marching_cubes on the fp32 cube, which is
     never downloaded); `render` keeps the reference's host post-processing (PyMCubes, trimesh) wherever PyMCubes imports and
-    cfg.mesh_backend does not say "device".  The lattice itself comes from the dataset: the reference's `pts` and `inside`, or
+    cfg.mesh_backend does not say "device"; cfg.mesh_components / cfg.mesh_color (off unless set) add the device-only clean-up of stray
+    components and a colour per vertex (`extract_mesh`, csrc/nb_mesh_clean.hip).  The lattice itself comes from the dataset: the reference's `pts` and `inside`, or
     the three axes and the device-carved `inside` of neuralbody_amd/mesh_lattice.py."""
 
     PAD = 10  # np.pad(cube, 10), if_mesh_renderer.py:46
@@ -450,17 +461,29 @@ class RendererMesh(Renderer):
         """-> DEVICE float32 tensor [X+2*pad, Y+2*pad, Z+2*pad]: alpha at the inside lattice points, 0 elsewhere.
         A batch that carries the lattice's axes (`axis_x`, `axis_y`, `axis_z`: neuralbody_amd/mesh_lattice.py) never holds the
         [X,Y,Z,3] points: see `_density_cube_axes`.  A batch with `pts` is the reference dataset's."""
+        return self._density_cube(batch, pad)[0]
+
+    def _density_cube(self, batch, pad=PAD):
+        """density_cube and what it decoded from: -> (cube, volumes), `volumes()` giving the frame's (feature_volume, sp_input)
+        to whoever has more to ask of them (the vertex colours of `extract_mesh`): a frame is encoded once, when first needed."""
+        made = []
+
+        def volumes():
+            if not made:
+                sp_input = self.prepare_sp_input(batch)
+                made.append((self.net.encode_sparse_voxels(sp_input), sp_input))
+            return made[0]
+
         if "axis_x" in batch:
-            return self._density_cube_axes(batch, pad)
+            return self._density_cube_axes(batch, pad, volumes), volumes
         pts = batch["pts"]
         inside = batch["inside"][0].bool()
         wpts = pts[0][inside][None].contiguous()
-        sp_input = self.prepare_sp_input(batch)
-        feature_volume = self.net.encode_sparse_voxels(sp_input)
+        feature_volume, sp_input = volumes()
         alpha = self.net.calculate_density(wpts, feature_volume, sp_input)
         cube = torch.zeros(pts.shape[1:-1], dtype=torch.float32, device=pts.device)
         cube[inside] = alpha[0, :, 0]
-        return torch.nn.functional.pad(cube, (pad,) * 6)
+        return torch.nn.functional.pad(cube, (pad,) * 6), volumes
 
     @staticmethod
     def _axes(batch):
@@ -471,7 +494,7 @@ class RendererMesh(Renderer):
                 [tuple(a.shape) for a in axes],))
         return [a[0].contiguous() for a in axes]
 
-    def _density_cube_axes(self, batch, pad):
+    def _density_cube_axes(self, batch, pad, volumes):
         """nb_lattice_gather -> calculate_density -> nb_lattice_scatter into the padded cube.  The count pass of the gather runs
         first (cap 0) and its 8-byte `n_out` is the one read-back: it sizes the point list, like `pts[0][inside]` does."""
         axes = self._axes(batch)
@@ -485,34 +508,83 @@ class RendererMesh(Renderer):
         wpts = torch.empty((total, 3), dtype=torch.float32, device=inside.device)
         lin = torch.empty(total, dtype=torch.int32, device=inside.device)
         ops.lattice_gather(axes, inside, wpts, lin, scratch=scratch)
-        sp_input = self.prepare_sp_input(batch)
-        feature_volume = self.net.encode_sparse_voxels(sp_input)
+        feature_volume, sp_input = volumes()
         alpha = self.net.calculate_density(wpts[None], feature_volume, sp_input)
         return ops.lattice_scatter(alpha, lin, dims, pad)
+
+    def _world_frame(self, batch, like):
+        """(step [3], origin [3]) of the lattice as tensors like `like`: the spacing read from the lattice and wbounds[0]."""
+        if "pts" in batch:
+            pts = batch["pts"]
+            step = torch.stack([pts[0, 1, 0, 0, 0] - pts[0, 0, 0, 0, 0], pts[0, 0, 1, 0, 1] - pts[0, 0, 0, 0, 1],
+                                pts[0, 0, 0, 1, 2] - pts[0, 0, 0, 0, 2]]).to(like)
+        else:
+            step = torch.stack([a[1] - a[0] for a in self._axes(batch)]).to(like)
+        return step, batch["wbounds"][0, 0].to(like)
 
     def _to_world(self, vertices, batch, pad=PAD):
         """Lattice index units of the padded cube -> world units: (v - pad) * step + wbounds[0] (the two lines the reference
         leaves commented out, if_mesh_renderer.py:49-50, with the step read from the lattice instead of the literal 0.005)."""
-        if "pts" in batch:
-            pts = batch["pts"]
-            step = torch.stack([pts[0, 1, 0, 0, 0] - pts[0, 0, 0, 0, 0], pts[0, 0, 1, 0, 1] - pts[0, 0, 0, 0, 1],
-                                pts[0, 0, 0, 1, 2] - pts[0, 0, 0, 0, 2]]).to(vertices)
-        else:
-            step = torch.stack([a[1] - a[0] for a in self._axes(batch)]).to(vertices)
-        return (vertices - float(pad)) * step + batch["wbounds"][0, 0].to(vertices)
+        step, origin = self._world_frame(batch, vertices)
+        return (vertices - float(pad)) * step + origin
 
-    def extract_mesh(self, batch, world=False, cube=None):
+    def extract_mesh(self, batch, world=False, cube=None, components="all", colors=False, volumes=None):
         """-> DEVICE (vertices [V,3] float32, triangles [T,3] int32) of the iso-surface cube == cfg.mesh_th (ops.marching_cubes;
-        the cube stays on the device).  Vertices in index units of the padded cube like PyMCubes', or in world units."""
+        the cube stays on the device).  Vertices in index units of the padded cube like PyMCubes', or in world units.
+        components: "all" — every closed surface the threshold leaves, what marching cubes returns (no further launch);
+        "largest" — the connected component of most triangles alone; a float f in (0, 1] — every component of at least
+        ceil(f * largest) triangles (ops.mesh_components, mesh_component_select, mesh_compact: vertices and triangles keep their
+        order, so the result is the marching-cubes mesh of the kept surfaces alone).
+        colors: the result is a `ColoredMesh` (a tuple that starts with the same two tensors) which also carries rgb_f float32
+        [V,3] and rgb_u8 uint8 [V,3], the colour head's answer at every vertex of the (cleaned) mesh, seen along -normal from
+        outside, the normals being those of the WORLD vertices; and wpts, viewdir, normals, what the head was asked.  ONE
+        calculate_density_color call on the feature volumes the cube was decoded from: `volumes` is what `_density_cube` returned
+        beside `cube` (with neither given, both are made here; the frame is encoded once)."""
         if cube is None:
-            cube = self.density_cube(batch)
+            cube, volumes = self._density_cube(batch)
         vertices, triangles = ops.marching_cubes(cube.contiguous(), self.cfg.mesh_th)
-        return (self._to_world(vertices, batch) if world else vertices), triangles
+        if ops.mesh_components_fraction(components) is not None:
+            scratch = ops.mesh_clean_scratch(vertices.shape[0], triangles.shape[0], vertices.device)
+            label = ops.mesh_components(triangles, vertices.shape[0], scratch=scratch)
+            keep, _ = ops.mesh_component_select(label, triangles, components, scratch=scratch)
+            vertices, triangles = ops.mesh_compact(vertices, triangles, keep, scratch=scratch)
+        if not colors:
+            return (self._to_world(vertices, batch) if world else vertices), triangles
+        if volumes is None:  # a cube from elsewhere: its frame is encoded here
+            volumes = self._volumes(batch)
+        wverts = self._to_world(vertices, batch)
+        normals = ops.mesh_vertex_normals(wverts, triangles)
+        step, origin = self._world_frame(batch, vertices)
+
+        def decode(wpts, viewdir):
+            feature_volume, sp_input = volumes()
+            return self.net.calculate_density_color(wpts, viewdir, feature_volume, sp_input)
+
+        rgb_f, rgb_u8, wpts, viewdir = ops.mesh_vertex_colors(vertices, normals, step.contiguous(), origin.contiguous(), self.PAD, decode)
+        return ColoredMesh(wverts if world else vertices, triangles, rgb_f, rgb_u8, wpts, viewdir, normals)
+
+    def _volumes(self, batch):
+        sp_input = self.prepare_sp_input(batch)
+        held = (self.net.encode_sparse_voxels(sp_input), sp_input)
+        return lambda: held
 
     def render(self, batch):
+        """if_mesh_renderer.py:26-54 -> {"cube", "mesh"}.  cfg.mesh_components / cfg.mesh_color (YAML-only keys like mesh_render,
+        absent = off) ask for `extract_mesh`'s clean-up and vertex colours: with either set the mesh is extracted on the device
+        whatever cfg.mesh_backend says (PyMCubes has neither), and `mesh` is a mesh.TriMesh, the class that carries
+        vertex_colors."""
         backend = getattr(self.cfg, "mesh_backend", "auto")
         if backend not in ("auto", "device"):
             raise ValueError("mesh_backend must be 'auto' or 'device', got %r" % (backend,))
+        components, colors = getattr(self.cfg, "mesh_components", "all"), bool(getattr(self.cfg, "mesh_color", False))
+        if ops.mesh_components_fraction(components) is not None or colors:
+            from .mesh import TriMesh
+
+            cube_dev, volumes = self._density_cube(batch)
+            mesh = self.extract_mesh(batch, cube=cube_dev, components=components, colors=colors, volumes=volumes)
+            cube = cube_dev.double().cpu().numpy()
+            return {"cube": cube, "mesh": TriMesh(mesh[0].double().cpu().numpy(), mesh[1].cpu().numpy(),
+                                                  vertex_colors=mesh.rgb_u8.cpu().numpy() if colors else None)}
         mcubes = None
         if backend == "auto":
             try:
