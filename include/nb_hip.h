@@ -148,9 +148,9 @@ int nb_mlp_latent_bias(const nb_mlp_params *p, const float *latent_row, float *o
  *   urows dev [(sum of n_rows_max) + 1][512] uint16: level l's rows start at row sum_{k<l} n_rows_max[k]; the last row is
  *   zero-filled by the call (sum of n_rows_max < 2^21).  Exact fp32 products (v_mfma_f32_32x32x2_f32), then head = fp16(u),
  *   remainder = fp16(u - head).  n_saturated dev [1] int32 or NULL, ZEROED BY THE CALLER (the call adds to it; the
- *   encoder's one zero fill covers it): how many products were beyond the fp16 range (+-65504: clamped) or not finite (a NaN
- *   product stays NaN in the planes) — the planes then do not carry fc_0 . V, use
- *   NB_PREC_F32 for such weights / volumes.
+ *   encoder's one zero fill covers it): zero iff no product of a live row was beyond the fp16 range (+-65504: clamped) or not
+ *   finite (a NaN product stays NaN in the planes), otherwise a positive lower bound of their number (the lanes that saw one, not
+ *   the products) — the planes then do not carry fc_0 . V, use NB_PREC_F32 for such weights / volumes.
  * nb_sparsify — active set of a DENSE volume that did not come with one (volumes handed to Network.calculate_density_color by a
  * caller other than encode_sparse_voxels): a voxel is active iff any channel is non-zero.  grid dev [D*H*W] int32 out (row id
  * or -1), rows_lin dev [n_rows_max] out (linear-voxel order), n_rows dev [1] out (clamped to n_rows_max; rows beyond it are

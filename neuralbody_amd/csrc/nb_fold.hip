@@ -33,7 +33,7 @@ struct FoldArgs {
     const float *w0;   // [256, 352]
     unsigned short *urows;
     int zero_row;
-    int *n_sat;        // optional: how many products left the fp16 range (or are not finite)
+    int *n_sat;        // optional: added to when products left the fp16 range (or are not finite): the lanes that saw one
 };
 
 // one workgroup = 128 rows x 256 outputs of one level; wave w = outputs [64 w, 64 w + 64)
@@ -122,7 +122,10 @@ __device__ __forceinline__ void fold_rows_level(const FoldArgs &a, int L, int ti
         }
     }
     // (rows beyond n are zero-staged: their products are 0)
-    if (a.n_sat && __builtin_amdgcn_ballot_w64(sat) != 0ull && lane == 0) atomicAdd(a.n_sat, __builtin_popcountll(__builtin_amdgcn_ballot_w64(sat)));
+    // the ballot with the whole wave active: taken inside the lane == 0 branch it saw lane 0's flag alone, and a wave whose offending
+    // products all sat in other lanes added nothing
+    const unsigned long long sat_lanes = __builtin_amdgcn_ballot_w64(sat);
+    if (a.n_sat && sat_lanes != 0ull && lane == 0) atomicAdd(a.n_sat, __builtin_popcountll(sat_lanes));
 }
 
 __global__ __launch_bounds__(256, 2) void nb_fold_rows_kernel(FoldArgs a) {
