@@ -123,4 +123,18 @@ __device__ __forceinline__ unsigned fp6_e2m3_bits(float v) {
     return sgn | code;
 }
 
+// view_fc column of encoding slot `slot` (0..31) of axis a: [x, (sin, cos)(x 2^k) k<10, v, (sin, cos)(v 2^k) k<4, 0, 0]; -1 = zero pad
+// (the order in which the march's owner lanes convert their encodings, and so the order the stream's packer lays the weights out in)
+__host__ __device__ inline int pe_slot_col(int a, int slot) {
+    if (a >= 3 || slot >= 30) return -1;
+    if (slot == 0) return 256 + 27 + a;
+    if (slot <= 20) {
+        const int k = (slot - 1) >> 1, is_cos = (slot - 1) & 1;
+        return 256 + 27 + 3 + 6 * k + 3 * is_cos + a;
+    }
+    if (slot == 21) return 256 + a;
+    const int k = (slot - 22) >> 1, is_cos = (slot - 22) & 1;
+    return 256 + 3 + 6 * k + 3 * is_cos + a;
+}
+
 }  // namespace nbm

@@ -26,6 +26,7 @@
 //   ATen grid_sampler_3d (trilinear, zeros padding, align_corners=True)
 
 #include "nb_march_common.h"
+#include "nb_pack_layout.h"
 
 using namespace nbm;
 
@@ -34,24 +35,7 @@ using namespace nbm;
 
 namespace {
 
-// ---------------------------------------------------------------- packed blob layout (floats)
-constexpr int G0 = 44;  // fc_0: 352 inputs = 176 K=2 chunks = 44 groups of 4 chunks
-constexpr int GH = 32;  // hidden 256 inputs = 128 chunks = 32 groups
-constexpr int GV = 44;  // view_fc: 128 chunks (latent_fc out) + 45 PE chunks + 3 zero chunks
-constexpr int OFF_L0 = 0;
-constexpr int OFF_B0 = OFF_L0 + 8 * G0 * 256;
-constexpr int OFF_L1 = OFF_B0 + 256;
-constexpr int OFF_B1 = OFF_L1 + 8 * GH * 256;
-constexpr int OFF_L2 = OFF_B1 + 256;
-constexpr int OFF_B2 = OFF_L2 + 8 * GH * 256;
-constexpr int OFF_AW = OFF_B2 + 256;  // alpha_fc weights [2][128]
-constexpr int OFF_AB = OFF_AW + 256;  // alpha_fc bias (4 floats, 1 used)
-constexpr int OFF_L4 = OFF_AB + 4;    // merged latent_fc[:, :256] @ feature_fc
-constexpr int OFF_LV = OFF_L4 + 8 * GH * 256;
-constexpr int OFF_BV = OFF_LV + 4 * GV * 256;
-constexpr int OFF_RW = OFF_BV + 128;  // rgb_fc weights [3][2][64]
-constexpr int OFF_RB = OFF_RW + 384;  // rgb_fc bias (4 floats, 3 used)
-constexpr int PACK_SIZE = OFF_RB + 4;
+// the packed blob's fp32 section (G0 / GH / GV, OFF_*, PACK_SIZE): nb_pack_layout.h
 
 // ---------------------------------------------------------------- one MLP layer on MFMA
 // The A-operand stream of a layer is NT*NG consecutive 1-KiB fragments; it is software-pipelined
@@ -449,10 +433,9 @@ __global__ __launch_bounds__(256) void nb_latent_bias_kernel(nb_mlp_params p, co
 
 extern "C" {
 
-static long long fold_stream_off() { return PACK_SIZE; }
-int64_t nb_mlp_pack_size(void) { return fold_stream_off() + nbm::fold_stream_floats(); }
+int64_t nb_mlp_pack_size(void) { return BLOB_FLOATS; }
 int64_t nb_mlp_latent_bias_size(void) { return 384; }
-int64_t nb_mlp_six_bit_stats_offset(void) { return nb_mlp_pack_size() - 8; }
+int64_t nb_mlp_six_bit_stats_offset(void) { return STATS_OFF; }
 
 static int check_params(const nb_mlp_params *p) {
     NB_REQUIRE(p != nullptr, "nb_mlp_params is NULL");
@@ -474,7 +457,7 @@ int nb_mlp_pack_sections(const nb_mlp_params *p, float *packed, int sections, vo
     hipLaunchKernelGGL(nb_pack_kernel, dim3(nb_ceil_div(PACK_SIZE, 256)), dim3(256), 0, (hipStream_t)stream, *p, packed);
     NB_CHECK_LAUNCH("nb_pack_kernel");
     if (sections & NB_PACK_F16F6)
-        if (int rc = nbm::pack_fold_stream(p, packed, fold_stream_off(), (hipStream_t)stream)) return rc;
+        if (int rc = nbm::pack_fold_stream(p, packed, (hipStream_t)stream)) return rc;
     return NB_OK;
 }
 
@@ -509,7 +492,7 @@ int nb_decode_points(const nb_scene *scene, const float *packed, const float *la
     hipStream_t st = (hipStream_t)stream;
     if (precision == NB_PREC_F16F6) {
         if (int rc = fill_fold(scene, &a.fold)) return rc;
-        return nbm::launch_points_fold(a, density_only, fold_stream_off(), st);
+        return nbm::launch_points_fold(a, density_only, st);
     }
     for (int l = 0; l < 4; ++l) NB_REQUIRE(scene->vol[l] != nullptr, "nb_decode_points: NB_PREC_F32 reads nb_scene.vol[%d]", l);
     if (density_only) hipLaunchKernelGGL((nb_points_kernel<true, false>), grid, block, 0, st, a);
@@ -550,7 +533,7 @@ int nb_march(const nb_scene *scene, const float *packed, const float *latent_bia
             a.ill = static_cast<float *>(ill_scratch);
             a.ill_cap = (int)(cap < (1 << 24) ? cap : (1 << 24));
         }
-        return nbm::launch_march_fold(a, fold_stream_off(), (hipStream_t)stream);
+        return nbm::launch_march_fold(a, (hipStream_t)stream);
     }
     for (int l = 0; l < 4; ++l) NB_REQUIRE(scene->vol[l] != nullptr, "nb_march: NB_PREC_F32 reads nb_scene.vol[%d]", l);
     hipLaunchKernelGGL(nb_march_kernel, dim3(a.n_wave_groups), dim3(256), 0, (hipStream_t)stream, a);

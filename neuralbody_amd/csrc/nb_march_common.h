@@ -1,5 +1,6 @@
 // nb_march_common.h — device code shared by the exact-fp32 (nb_march.hip) and the fc_0-folded f16f6 (nb_march_fold.hip)
-// decode / march kernels: scene + argument structs, feature-vector layout, the fp32 kernel's trilinear gather,
+// decode / march kernels, the latter's fix-up (nb_march_fixup.hip) and the packer of its weight stream (nb_march_pack.hip):
+// scene + argument structs, feature-vector layout, the MFMA fragment order and its inverse, the fp32 kernel's trilinear gather,
 // positional encoding, sampling helpers, compositing, XCD-aware block remap.
 #pragma once
 #include "nb_common.h"
@@ -25,6 +26,15 @@ __device__ __forceinline__ float relu1(float x) {
 
 // feature row (within a 32-row tile) held by accumulator register r of a lane with half index hi
 __host__ __device__ constexpr int tile_row(int r, int hi) { return (r & 3) + 8 * (r >> 2) + 4 * hi; }
+// ... and its inverse: feature row `row` (0..31) of a tile is register tile_reg(row) of the lanes with half index tile_hi(row)
+__host__ __device__ constexpr int tile_hi(int row) { return (row >> 2) & 1; }
+__host__ __device__ constexpr int tile_reg(int row) { return (row & 3) + 4 * (row >> 3); }
+constexpr bool tile_row_round_trip() {
+    for (int row = 0; row < 32; ++row)
+        if (tile_reg(row) >= 16 || tile_row(tile_reg(row), tile_hi(row)) != row) return false;
+    return true;
+}
+static_assert(tile_row_round_trip(), "tile_reg / tile_hi invert tile_row on all 32 rows of a tile");
 
 // channel layout of the gathered feature vector (latent_xyzc.py:63-71)
 __host__ __device__ constexpr int lvl_c(int l) { return l == 0 ? 32 : (l == 1 ? 64 : 128); }
@@ -38,6 +48,8 @@ __host__ __device__ inline int col_feat(int q, int hi) {
 }
 // input column for accumulator element q = 16 * tile + r of the previous layer
 __host__ __device__ inline int col_hidden(int q, int hi) { return 32 * (q >> 4) + tile_row(q & 15, hi); }
+// ... and its inverse: hidden column col is element hidden_q(col) of the lanes with half index tile_hi(col & 31)
+__host__ __device__ constexpr int hidden_q(int col) { return 16 * (col >> 5) + tile_reg(col & 31); }
 // view_fc column (346 = 256 + 27 + 63, latent_xyzc.py:113-118) for PE slot c, -1 = zero pad
 __host__ __device__ inline int col_pe(int c, int hi) {
     if (c < 12) {  // view direction, frequency k = c/3, axis a = c%3: hi=0 sin, hi=1 cos
@@ -644,11 +656,12 @@ inline void fill_march_args(MarchArgs &a, const float *packed, const float *late
     a.n_wave_groups = nb_ceil_div(n_rays, 128);
 }
 
-// fc_0 folded into the volumes, fp16 + scaled-6-bit for the remaining layers (nb_march_fold.hip); stream_off = float offset of
-// its weight stream inside the packed blob, stats: 6 ints behind it (nb_mlp_six_bit_stats_offset)
-long long fold_stream_floats();
-int pack_fold_stream(const nb_mlp_params *p, float *packed, long long stream_off, hipStream_t st);
-int launch_march_fold(MarchArgs a, long long stream_off, hipStream_t st);
-int launch_points_fold(MarchArgs a, int density_only, long long stream_off, hipStream_t st);
+// fc_0 folded into the volumes, fp16 + scaled-6-bit for the remaining layers: the march and point kernels (nb_march_fold.hip),
+// the last-sample fix-up behind a march (nb_march_fixup.hip) and the packer of their weight stream (nb_march_pack.hip).  Where the
+// stream and its statistic lie inside the packed blob is nb_pack_layout.h's to say (STREAM_OFF, STATS_OFF).
+int pack_fold_stream(const nb_mlp_params *p, float *packed, hipStream_t st);
+int launch_march_fold(MarchArgs a, hipStream_t st);
+int launch_march_fixup(const MarchArgs &a, hipStream_t st);
+int launch_points_fold(MarchArgs a, int density_only, hipStream_t st);
 
 }  // namespace nbm

@@ -37,70 +37,19 @@
 // Per-sample work (ray set-up, positional encoding, compositing) is done by "owner" lanes: wave w, lane l owns sample
 // 16 w + (l & 15) and, of that sample, pyramid level / axis `part` = l >> 4.
 #include "nb_f6_ops.h"
+#include "nb_fold_level.h"
 #include "nb_march_hooks.h"
+#include "nb_pack_layout.h"
 
 using namespace nbm;
 
 namespace {
 
-// ---------------------------------------------------------------- weight stream (per wave), in 1-KiB pieces
-// phase = NB K blocks x MT output tiles of this wave (wave w's b-th block of a phase over published activations is LDS block
-// (b + w) & 3: it starts with the block it has published itself, layer_s); per block: for each of its 4 chunks, for each tile:
-// A16 (1 piece: the fp16 heads, the main product); then its two CROSS TERMS in execution order, for each tile one fragment: k = 0 W_h (multiplies the
-// remainder operand), k = 1 W_l (multiplies the head operand).  A cross fragment is fp6 e2m3 — 24 bytes of data + its E8M0 scale
-// in the lane's seventh dword, 2 pieces — or, for the terms in NB_FP4_TERMS (bit k), fp4 e2m1 — 16 bytes of data, 1 piece, its
-// scale one byte of the block's SCALE DWORD (byte k MT + m; one 256-byte load per block from behind the pieces).  The cross
-// terms are 2^-11 of the main term, so their weight operand needs few bits: fp4 takes the stream from 176 to 132 pieces per wave
-// and depth step — the stream (L2 -> L1, 64 B/clk/CU) is what the MFMA phases wait for (profiles/r06_march_premises.log) — for
-// 2^-13 instead of 2^-15 relative error per term (profiles/r06_precision_fp4.md).
-#ifndef NB_FP4_TERMS
-#define NB_FP4_TERMS 3
-#endif
-constexpr bool FP4_K[2] = {(NB_FP4_TERMS & 1) != 0, (NB_FP4_TERMS & 2) != 0};
+// ---------------------------------------------------------------- weight stream (per wave): its pieces, phases and scale dwords are
+// laid out in nb_pack_layout.h; the kernel reads it through a register ring
 constexpr bool ANY_FP4 = FP4_K[0] || FP4_K[1];
-// six-bit fragments are two pieces = one (even-aligned) ring entry: when only W_h is four-bit its fragment goes second
-constexpr int TERM_ORDER[2] = {(FP4_K[0] && !FP4_K[1]) ? 1 : 0, (FP4_K[0] && !FP4_K[1]) ? 0 : 1};
-__host__ __device__ constexpr int term_pieces(int k) { return FP4_K[k] ? 1 : 2; }
-// pieces per block (rounded to even: the next block's six-bit fragments stay even-aligned; an odd count leaves one hole)
-__host__ __device__ constexpr int block_pieces(int mt) { return (4 * mt + mt * term_pieces(0) + mt * term_pieces(1) + 1) & ~1; }
-// first piece (inside its block) of the fragment of the cross term executed `slot`-th (0 / 1), tile m
-__host__ __device__ constexpr int cross_piece(int mt, int slot, int m) {
-    return 4 * mt + (slot == 0 ? 0 : mt * term_pieces(TERM_ORDER[0])) + m * term_pieces(TERM_ORDER[slot]);
-}
 constexpr int S_R = 8;  // register ring depth in pieces
-__host__ __device__ constexpr int phase_pieces(int nb, int mt) { return nb * block_pieces(mt); }
-constexpr int N_PH = 4;
-// fc_1, fc_2, the folded colour head over fc_2's outputs (one tile per wave), view_fc over the positional encodings
-constexpr int PH_NB[N_PH] = {4, 4, 4, 2};
-constexpr int PH_MT[N_PH] = {2, 2, 1, 1};
-__host__ __device__ constexpr int phase_p0(int ph) {
-    int p = 0;
-    for (int i = 0; i < ph; ++i) p += phase_pieces(PH_NB[i], PH_MT[i]);
-    return p;
-}
-__host__ __device__ constexpr int phase_s0(int ph) {  // first scale dword of the phase (one per block)
-    int n = 0;
-    for (int i = 0; i < ph; ++i) n += PH_NB[i];
-    return n;
-}
-constexpr int P_L1 = phase_p0(0), P_L2 = phase_p0(1), P_VG = phase_p0(2), P_VP = phase_p0(3), P_TOTAL = phase_p0(4);
-constexpr int N_SCALE = phase_s0(4);                        // 14 scale dwords (256 bytes each) behind the pieces
-constexpr int WAVE_STREAM = P_TOTAL * 1024 + ((N_SCALE * 256 + 1023) & ~1023);  // bytes of one wave's share of the stream
-static_assert(P_TOTAL == (NB_FP4_TERMS == 3 ? 132 : (NB_FP4_TERMS == 0 ? 176 : 160)), "pieces per wave per depth step");
-static_assert(S_R % 2 == 0 && P_L1 % 2 == 0 && P_L2 % 2 == 0 && P_VG % 2 == 0 && P_VP % 2 == 0, "six-bit fragments on even pieces");
-__host__ __device__ constexpr int phase_of_p0(int p0) { return p0 == P_L1 ? 0 : (p0 == P_L2 ? 1 : (p0 == P_VG ? 2 : 3)); }
-
-// fp32 section of the packed blob (written by nb_pack_kernel, nb_march.hip): offsets in floats
-constexpr int F_OFF_B0 = 8 * 44 * 256;
-constexpr int F_OFF_B1 = F_OFF_B0 + 256 + 8 * 32 * 256;
-constexpr int F_OFF_B2 = F_OFF_B1 + 256 + 8 * 32 * 256;
-constexpr int F_OFF_AW = F_OFF_B2 + 256;
-constexpr int F_OFF_AB = F_OFF_AW + 256;
-constexpr int F_OFF_L4 = F_OFF_AB + 4;
-constexpr int F_OFF_LV = F_OFF_L4 + 8 * 32 * 256;
-constexpr int F_OFF_BV = F_OFF_LV + 4 * 44 * 256;
-constexpr int F_OFF_RW = F_OFF_BV + 128;
-constexpr int F_OFF_RB = F_OFF_RW + 384;
+static_assert(S_R % 2 == 0, "six-bit fragments on even pieces");
 
 // ---------------------------------------------------------------- LDS
 constexpr int CH_BYTES = 2048;                 // one K=16 chunk: 2 N tiles x 1 KiB B fragment (64 lanes x 8 fp16)
@@ -456,11 +405,6 @@ __device__ __forceinline__ void publish_s(f32x16 (&acc)[2][2], HalfBlock (&h)[2]
 typedef short s4v __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) s4v *lds_s4p;
 
-// unnorm_clamped (nb_march_common.h) with the level's (float)(size - 1) and (float)size + 1 given
-__device__ __forceinline__ float unnorm_s(float gcoord, float fm1, float fp1) {
-    const float i = __fmul_rn(__fdiv_rn(__fadd_rn(gcoord, 1.f), 2.f), fm1);
-    return fminf(fmaxf(i, -2.f), fp1);
-}
 // a * b + c on the full-rate 24-bit multiplier; |a|, |b| < 2^23
 __device__ __forceinline__ int mad24(int a, int b, int c) {
     int r;
@@ -488,13 +432,6 @@ __device__ __forceinline__ int red_max16i(int v) {
     return v;
 }
 
-// the lane's pyramid level (part): sizes, unnormalisation constants, index grid, first U row
-struct Lvl {
-    int D, H, W;
-    float fmx, fmy, fmz, fpx, fpy, fpz;
-    const int *grid;
-    int rbase;
-};
 __device__ __forceinline__ Lvl load_lvl(const char *actz, int part) {
     const i32x4 *p = reinterpret_cast<const i32x4 *>(actz + LC_OFF + part * 48);
     const i32x4 a = p[0], b = p[1], c = p[2];
@@ -505,20 +442,6 @@ __device__ __forceinline__ Lvl load_lvl(const char *actz, int part) {
     l.grid = reinterpret_cast<const int *>(((unsigned long long)(unsigned)c.z << 32) | (unsigned long long)(unsigned)c.y);
     l.rbase = c.w;
     return l;
-}
-struct LvlIdx {
-    float ix, iy, iz;
-    int x0, y0, z0;
-};
-__device__ __forceinline__ LvlIdx level_index(const Lvl &lv, const GridCoord &g) {
-    LvlIdx q;
-    q.ix = unnorm_s(g.gw, lv.fmx, lv.fpx);
-    q.iy = unnorm_s(g.gh, lv.fmy, lv.fpy);
-    q.iz = unnorm_s(g.gd, lv.fmz, lv.fpz);
-    q.x0 = (int)floorf(q.ix);
-    q.y0 = (int)floorf(q.iy);
-    q.z0 = (int)floorf(q.iz);
-    return q;
 }
 
 // boxes: this lane's sample (if `take`) -> clamped [floor, floor + 1] of its level, merged over the 16 lanes of (wave, level);
@@ -949,19 +872,6 @@ __device__ __forceinline__ void composite_step(char *actz, const float *pk, int 
     }
 }
 
-// view_fc column of encoding slot `slot` (0..31) of axis a: [x, (sin, cos)(x 2^k) k<10, v, (sin, cos)(v 2^k) k<4, 0, 0]; -1 = zero pad
-__host__ __device__ inline int pe_slot_col(int a, int slot) {
-    if (a >= 3 || slot >= 30) return -1;
-    if (slot == 0) return 256 + 27 + a;
-    if (slot <= 20) {
-        const int k = (slot - 1) >> 1, is_cos = (slot - 1) & 1;
-        return 256 + 27 + 3 + 6 * k + 3 * is_cos + a;
-    }
-    if (slot == 21) return 256 + a;
-    const int k = (slot - 22) >> 1, is_cos = (slot - 22) & 1;
-    return 256 + 3 + 6 * k + 3 * is_cos + a;
-}
-
 // ---------------------------------------------------------------- the kernel
 // FOLD_STAMP / FOLD_SUB / FOLD_DUMP: empty in the product build (nb_march_hooks.h); experiment builds pre-include
 // tools/experiments/fold_instrument.h (cycle stamps at the phase boundaries, per-layer accumulator taps)
@@ -1033,13 +943,13 @@ __global__ __launch_bounds__(256, 2) void nb_march_fold_kernel(MarchArgs a, cons
         float *prm = reinterpret_cast<float *>(lds + PRM_OFF);
         for (int i = tid; i < P_SIZE; i += 256) {
             float v;
-            if (i < P_B1) v = a.pk[F_OFF_B0 + i - P_B0];
-            else if (i < P_B2) v = a.pk[F_OFF_B1 + i - P_B1];
-            else if (i < P_AW) v = a.pk[F_OFF_B2 + i - P_B2];
-            else if (i < P_RW) v = a.pk[F_OFF_AW + i - P_AW];
-            else if (i < P_AB) v = a.pk[F_OFF_RW + i - P_RW];
-            else if (i < P_RB) v = a.pk[F_OFF_AB + i - P_AB];
-            else if (i < P_LB) v = a.pk[F_OFF_RB + i - P_RB];
+            if (i < P_B1) v = a.pk[OFF_B0 + i - P_B0];
+            else if (i < P_B2) v = a.pk[OFF_B1 + i - P_B1];
+            else if (i < P_AW) v = a.pk[OFF_B2 + i - P_B2];
+            else if (i < P_RW) v = a.pk[OFF_AW + i - P_AW];
+            else if (i < P_AB) v = a.pk[OFF_RW + i - P_RW];
+            else if (i < P_RB) v = a.pk[OFF_AB + i - P_AB];
+            else if (i < P_LB) v = a.pk[OFF_RB + i - P_RB];
             else v = DENSITY_ONLY ? 0.f : a.lb[256 + i - P_LB];  // bias of the folded view layer (nb_mlp_latent_bias, second block)
             prm[i] = v;
         }
@@ -1368,277 +1278,25 @@ __global__ __launch_bounds__(256, 2) void nb_march_fold_kernel(MarchArgs a, cons
     }
 }
 
-// ---------------------------------------------------------------- last-sample fix-up
-// The rays composite_step listed (their last density within NB_ILL_SIGMA of zero): one workgroup per record recomputes that ONE
-// density at fp32 level — fc_0 through the same folded planes (head + remainder = 22 bits of fc_0 . V, trilinear weights in fp32,
-// fp64 accumulation), fc_1 / fc_2 / alpha_fc from the fp32 fragments of the packed blob (fp64 accumulation, activations rounded to
-// fp32 between the layers like the reference's) — and composites the last sample again from the listed state, exactly as
-// RayAccum::add / store do.  Thread f owns natural feature f.
-__device__ __forceinline__ int frag_bias_index(int f) {  // natural feature f inside a [tile][hi][16] block (b_pack, nb_march.hip)
-    const int t = f >> 5, i = f & 31;
-    return (t * 2 + ((i >> 2) & 1)) * 16 + (i & 3) + 4 * (i >> 3);
-}
-// row `row` of a 256 x 256 layer stored as fp32 A fragments (a_pack kind 1): the 16 bytes at ((tile * 32 + g) * 64 + hi * 32 + row % 32)
-// hold the weights of input columns 8 g + 4 hi .. + 3 (col_hidden(4 g + i, hi) = 8 g + 4 hi + i)
-__device__ __forceinline__ double frag_row_dot(const float *wfrag, const float *h, int row) {
-    const f32x4 *w4 = reinterpret_cast<const f32x4 *>(wfrag) + (size_t)(row >> 5) * 32 * 64 + (row & 31);
-    double s = 0.0;
-    for (int g = 0; g < 32; ++g)
-#pragma unroll
-        for (int hi = 0; hi < 2; ++hi) {
-            const f32x4 w = w4[g * 64 + hi * 32];
-            const float *hh = h + 8 * g + 4 * hi;
-            s = fma((double)w.x, (double)hh[0], s);
-            s = fma((double)w.y, (double)hh[1], s);
-            s = fma((double)w.z, (double)hh[2], s);
-            s = fma((double)w.w, (double)hh[3], s);
-        }
-    return s;
-}
-__global__ __launch_bounds__(256) void nb_march_fixup_kernel(MarchArgs a) {
-    __shared__ float rec[NB_ILL_RECORD_FLOATS];
-    __shared__ float cw[32];
-    __shared__ int crow[32];
-    __shared__ float h[2][256];
-    __shared__ double red[4];
-    const int tid = threadIdx.x;
-    int *hdr = reinterpret_cast<int *>(a.ill);
-    const int n = min(hdr[0], a.ill_cap);
-    const int S = a.n_samples;
-    for (int it = blockIdx.x; it < n; it += gridDim.x) {
-        __syncthreads();
-        if (tid < NB_ILL_RECORD_FLOATS) rec[tid] = a.ill[NB_ILL_HEADER_FLOATS + (long long)it * NB_ILL_RECORD_FLOATS + tid];
-        __syncthreads();
-        const long long ray = __float_as_int(rec[0]);
-        const float z = rec[4];
-        if (tid < 32) {  // (level, corner): weight and U row, with the march's own arithmetic (prep_sequential, wt_build)
-            const int L = tid >> 3, corner = tid & 7;
-            const float px = __fadd_rn(a.ray_o[ray * 3 + 0], __fmul_rn(a.ray_d[ray * 3 + 0], z)),
-                        py = __fadd_rn(a.ray_o[ray * 3 + 1], __fmul_rn(a.ray_d[ray * 3 + 1], z)),
-                        pz = __fadd_rn(a.ray_o[ray * 3 + 2], __fmul_rn(a.ray_d[ray * 3 + 2], z));
-            const GridCoord g = grid_coords(a.sc, px, py, pz);
-            Lvl lv;
-            lv.D = a.sc.dhw[L][0]; lv.H = a.sc.dhw[L][1]; lv.W = a.sc.dhw[L][2];
-            lv.fmx = a.sc.fm1[L][2]; lv.fmy = a.sc.fm1[L][1]; lv.fmz = a.sc.fm1[L][0];
-            lv.fpx = a.sc.fp1[L][2]; lv.fpy = a.sc.fp1[L][1]; lv.fpz = a.sc.fp1[L][0];
-            const LvlIdx q = level_index(lv, g);
-            const float fx = (float)q.x0, fy = (float)q.y0, fz = (float)q.z0;
-            const int dx = corner & 1, dy = (corner >> 1) & 1, dz = corner >> 2;
-            const float wx = dx ? q.ix - fx : (fx + 1.f) - q.ix, wy = dy ? q.iy - fy : (fy + 1.f) - q.iy, wz = dz ? q.iz - fz : (fz + 1.f) - q.iz;
-            const int xx = q.x0 + dx, yy = q.y0 + dy, zz = q.z0 + dz;
-            const bool inb = (unsigned)xx < (unsigned)lv.W && (unsigned)yy < (unsigned)lv.H && (unsigned)zz < (unsigned)lv.D;
-            int row = -1;
-            if (inb) {
-                const int rid = a.fold.grid[L][((size_t)zz * lv.H + yy) * lv.W + xx];
-                if (rid >= 0) row = a.fold.row_base[L] + rid;
-            }
-            cw[tid] = (wx * wy) * wz;
-            crow[tid] = row;
-        }
-        __syncthreads();
-        {
-            double s = (double)a.pk[F_OFF_B0 + frag_bias_index(tid)];
-            for (int c = 0; c < 32; ++c) {
-                if (crow[c] < 0) continue;  // uniform
-                const _Float16 *u = reinterpret_cast<const _Float16 *>(a.fold.urows) + (size_t)crow[c] * 512;
-                s = fma((double)cw[c], (double)(float)u[tid] + (double)(float)u[256 + tid], s);
-            }
-            h[0][tid] = fmaxf((float)s, 0.f);
-        }
-        __syncthreads();
-        h[1][tid] = fmaxf((float)((double)a.pk[F_OFF_B1 + frag_bias_index(tid)] + frag_row_dot(a.pk + F_OFF_B0 + 256, h[0], tid)), 0.f);
-        __syncthreads();
-        const float h3 = fmaxf((float)((double)a.pk[F_OFF_B2 + frag_bias_index(tid)] + frag_row_dot(a.pk + F_OFF_B1 + 256, h[1], tid)), 0.f);
-        {
-            const int t = tid >> 5, i = tid & 31;  // alpha_fc: [hi][q] with column col_hidden(q, hi)
-            double p = (double)a.pk[F_OFF_AW + ((i >> 2) & 1) * 128 + 16 * t + (i & 3) + 4 * (i >> 3)] * (double)h3;
-#pragma unroll
-            for (int m = 32; m >= 1; m >>= 1) p += __shfl_xor(p, m);
-            if ((tid & 63) == 0) red[tid >> 6] = p;
-        }
-        __syncthreads();
-        if (tid == 0) {
-            const float sigma = (float)(((red[0] + red[1]) + (red[2] + red[3])) + (double)a.pk[F_OFF_AB]);
-            RayAccum ra;
-            ra.T = rec[1]; ra.depth = rec[2]; ra.accw = rec[3];
-            ra.cr = rec[8]; ra.cg = rec[9]; ra.cb = rec[10];
-            const float out4[4] = {rec[12], rec[13], rec[14], sigma};
-            const float w = ra.add(out4, z, rec[5]);
-            ra.store(a, ray);
-            a.weights[ray * S + (S - 1)] = w;
-            if (a.raw) a.raw[(ray * S + (S - 1)) * 4 + 3] = sigma;
-            if ((sigma > 0.f) != (rec[6] > 0.f)) atomicAdd(&hdr[1], 1);  // the march had taken the other branch of the step
-        }
-    }
-}
-
-// ---------------------------------------------------------------- weight stream packing
-// input column of the layer phase `ph` held by element e of half-block (b, kh) of LDS block b; -1 = zero padding
-__device__ __forceinline__ int phase_col(int ph, int b, int kh, int e) {
-    if (ph < 3) return col_hidden(32 * b + e, kh);
-    return pe_slot_col(2 * b + kh, e);  // the encodings: the owner lane's part
-}
-__device__ __forceinline__ float phase_weight(const nb_mlp_params &p, const float *f32_blob, int ph, int row, int b, int kh, int e) {
-    const int col = phase_col(ph, b, kh, e);
-    if (col < 0) return 0.f;
-    if (ph == 0) return p.fc1_w[row * 256 + col];
-    if (ph == 1) return p.fc2_w[row * 256 + col];
-    if (ph == 2) {
-        // view_w[:, :256] . (latent_w[:, :256] . feature_w): the inner product comes from the fp32 section (formed in fp64
-        // there, fragment order: invert col_hidden), the outer one is summed in fp64 here
-        const int tt = col >> 5, rr = col & 31, hi2 = (rr >> 2) & 1, r2 = (rr & 3) + 4 * (rr >> 3), q2 = 16 * tt + r2;
-        double s = 0.0;
-        for (int m = 0; m < 256; ++m)
-            s += (double)p.view_w[row * 346 + m] *
-                 (double)f32_blob[F_OFF_L4 + (((m >> 5) * 32 + (q2 >> 2)) * 64 + (hi2 * 32 + (m & 31))) * 4 + (q2 & 3)];
-        return (float)s;
-    }
-    return p.view_w[row * 346 + col];
-}
-
-// fp4 e2m1 (sign, 2 exponent bits of bias 1, 1 mantissa bit: 0 0.5 1 1.5 2 3 4 6), round to nearest (ties to the even code)
-__device__ __forceinline__ unsigned fp4_e2m1_bits(float v) {
-    const unsigned sgn = v < 0.f ? 8u : 0u;
-    const float a = fminf(fabsf(v), 6.f);
-    constexpr float grid[8] = {0.f, 0.5f, 1.f, 1.5f, 2.f, 3.f, 4.f, 6.f};
-    unsigned code = 0;
-    float best = a;
-    for (unsigned c = 1; c < 8; ++c) {
-        const float d = fabsf(a - grid[c]);
-        if (d < best || (d == best && (c & 1u) == 0u)) {
-            best = d;
-            code = c;
-        }
-    }
-    return sgn | code;
-}
-
-// one thread per (wave, piece, lane): the lane's 16 bytes (+, for a four-bit fragment, its scale byte in the block's scale dword)
-__global__ void nb_pack_fold_kernel(nb_mlp_params p, const float *__restrict__ f32_blob, unsigned *__restrict__ out, int *__restrict__ stats) {
-    const int t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= 4 * P_TOTAL * 64) return;
-    const int lane = t & 63, piece = (t >> 6) % P_TOTAL, w = (t >> 6) / P_TOTAL;
-    const int i = lane & 31, kg = lane >> 5;
-    int ph = 0, p0 = 0;
-    for (int q = 0; q < N_PH; ++q) {
-        const int n = phase_pieces(PH_NB[q], PH_MT[q]);
-        if (piece < p0 + n) {
-            ph = q;
-            break;
-        }
-        p0 += n;
-    }
-    const int mt = PH_MT[ph], ppb = block_pieces(mt);
-    const int rel = piece - p0, b = rel / ppb, r = rel % ppb;
-    // the LDS block whose columns step block b multiplies: wave w walks the published blocks from its own one (layer_s, OWN)
-    const int bl = ph < 3 ? (b + w) & 3 : b;
-    unsigned w32[4] = {0u, 0u, 0u, 0u};
-    if (r < 4 * mt) {  // A16 of chunk j, tile m
-        const int j = r / mt, m = r % mt;
-        const int row = (mt == 2 ? 64 * w + 32 * m : 32 * w) + i;
-        for (int q = 0; q < 8; q += 2) {
-            const f16x2 hp = {(_Float16)phase_weight(p, f32_blob, ph, row, bl, kg, 8 * j + q),
-                              (_Float16)phase_weight(p, f32_blob, ph, row, bl, kg, 8 * j + q + 1)};
-            w32[q / 2] = __builtin_bit_cast(unsigned, hp);
-        }
-    } else {  // a cross fragment: k = 0 W_h (multiplies the interleaved remainder operand), k = 1 W_l (natural order) — or the block's hole
-        int r6 = r - 4 * mt, k = -1, m = 0, half = 0;
-        for (int slot = 0; slot < 2; ++slot) {
-            const int kk = TERM_ORDER[slot], width = mt * term_pieces(kk);
-            if (r6 < width) {
-                k = kk;
-                m = r6 / term_pieces(kk);
-                half = r6 % term_pieces(kk);
-                break;
-            }
-            r6 -= width;
-        }
-        if (k >= 0) {
-            const bool four = FP4_K[k];
-            const float top = four ? 6.f : 7.5f;  // largest magnitude of the format
-            const int row = (mt == 2 ? 64 * w + 32 * m : 32 * w) + i;
-            float wv[32], amax = 0.f;
-            for (int e = 0; e < 32; ++e) {
-                const int n = k ? e : 16 * (e & 1) + (e >> 1);
-                const float wt = phase_weight(p, f32_blob, ph, row, bl, kg, n);
-                const float h = (float)(_Float16)wt;
-                wv[e] = k ? wt - h : h;
-                amax = fmaxf(amax, fabsf(wv[e]));
-            }
-            int ex = 0;
-            if (amax > 0.f && amax < 3.0e38f) {
-                ex = ilogbf(amax / top);
-                if (ldexpf(top, ex) < amax) ++ex;  // the smallest power of two with max / 2^ex <= top
-                ex = min(max(ex, -120), 120);
-            }
-            if (four) {
-                for (int e = 0; e < 32; ++e) w32[e >> 3] |= fp4_e2m1_bits(ldexpf(wv[e], -ex)) << (4 * (e & 7));
-                unsigned char *sc = reinterpret_cast<unsigned char *>(out) + (size_t)w * WAVE_STREAM + (size_t)P_TOTAL * 1024 +
-                                    (size_t)(phase_s0(ph) + b) * 256 + lane * 4 + (k * mt + m);
-                *sc = (unsigned char)(127 + ex);
-            } else {
-                unsigned w8[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
-                for (int e = 0; e < 32; ++e) {
-                    const unsigned code = fp6_e2m3_bits(ldexpf(wv[e], -ex));
-                    const int bit = 6 * e;
-                    w8[bit >> 5] |= code << (bit & 31);
-                    if ((bit & 31) > 26) w8[(bit >> 5) + 1] |= code >> (32 - (bit & 31));
-                }
-                w8[6] = (unsigned)(127 + ex);
-                for (int q = 0; q < 4; ++q) w32[q] = w8[4 * half + q];
-            }
-            // statistic behind nb_mlp_six_bit_stats_offset(): how many non-zero head weights sit below 1/8 of their block's
-            // maximum, i.e. where e2m3 keeps fewer than 3 bits and e2m1 none (per layer: small, non-zero)
-            if (k == 0 && half == 0) {
-                int small = 0, nz = 0;
-                for (int e = 0; e < 32; ++e) {
-                    nz += wv[e] != 0.f;
-                    small += wv[e] != 0.f && fabsf(wv[e]) < 0.125f * amax;
-                }
-                const int layer = ph < 2 ? ph : 2;  // fc_1, fc_2, the folded colour head (both of its K phases)
-                atomicAdd(&stats[2 * layer], small);
-                atomicAdd(&stats[2 * layer + 1], nz);
-            }
-        }
-    }
-    unsigned *dst = reinterpret_cast<unsigned *>(reinterpret_cast<char *>(out) + (size_t)w * WAVE_STREAM) + ((size_t)piece * 64 + lane) * 4;
-    for (int q = 0; q < 4; ++q) dst[q] = w32[q];
-}
-
 }  // namespace
 
 namespace nbm {
 
-long long fold_stream_floats() { return (long long)4 * WAVE_STREAM / 4 + 8; }  // + the six-bit statistic (6 ints, 2 pad)
-
-int pack_fold_stream(const nb_mlp_params *p, float *packed, long long stream_off, hipStream_t st) {
-    const long long n = (long long)4 * P_TOTAL * 64;
-    int *stats = reinterpret_cast<int *>(packed + stream_off + (long long)4 * WAVE_STREAM / 4);
-    NB_REQUIRE(hipMemsetAsync(stats, 0, 8 * sizeof(int), st) == hipSuccess, "pack_fold_stream: hipMemsetAsync failed");
-    hipLaunchKernelGGL(nb_pack_fold_kernel, dim3(nb_ceil_div(n, 256)), dim3(256), 0, st, *p, packed,
-                       reinterpret_cast<unsigned *>(packed + stream_off), stats);
-    NB_CHECK_LAUNCH("nb_pack_fold_kernel");
-    return NB_OK;
-}
-
-int launch_march_fold(MarchArgs a, long long stream_off, hipStream_t st) {
+int launch_march_fold(MarchArgs a, hipStream_t st) {
     a.n_wave_groups = (int)nb_ceil_div(a.ray_order ? a.n_slots : a.n_rays, 64);
-    const char *stream = reinterpret_cast<const char *>(a.pk + stream_off);
+    const char *stream = reinterpret_cast<const char *>(a.pk + STREAM_OFF);
     if (a.ill) NB_REQUIRE(hipMemsetAsync(a.ill, 0, NB_ILL_HEADER_FLOATS * sizeof(float), st) == hipSuccess, "nb_march: hipMemsetAsync(ill_scratch) failed");
     if (a.cull.n_views) hipLaunchKernelGGL((nb_march_fold_kernel<0, true>), dim3(a.n_wave_groups), dim3(256), 0, st, a, stream);
     else hipLaunchKernelGGL((nb_march_fold_kernel<0, false>), dim3(a.n_wave_groups), dim3(256), 0, st, a, stream);
     NB_CHECK_LAUNCH("nb_march_fold_kernel");
-    if (a.ill) {
-        hipLaunchKernelGGL(nb_march_fixup_kernel, dim3(NB_ILL_FIXUP_BLOCKS), dim3(256), 0, st, a);
-        NB_CHECK_LAUNCH("nb_march_fixup_kernel");
-    }
+    if (a.ill) return launch_march_fixup(a, st);
     return NB_OK;
 }
 
 // nb_decode_points on the same kernel: every point a one-sample ray whose decoder output is stored instead of composited
-int launch_points_fold(MarchArgs a, int density_only, long long stream_off, hipStream_t st) {
+int launch_points_fold(MarchArgs a, int density_only, hipStream_t st) {
     a.n_wave_groups = (int)nb_ceil_div(a.n_pts, 64);
-    const char *stream = reinterpret_cast<const char *>(a.pk + stream_off);
+    const char *stream = reinterpret_cast<const char *>(a.pk + STREAM_OFF);
     if (density_only) hipLaunchKernelGGL((nb_march_fold_kernel<2, false>), dim3(a.n_wave_groups), dim3(256), 0, st, a, stream);
     else hipLaunchKernelGGL((nb_march_fold_kernel<1, false>), dim3(a.n_wave_groups), dim3(256), 0, st, a, stream);
     NB_CHECK_LAUNCH("nb_march_fold_kernel (points)");

@@ -1,4 +1,5 @@
-// nb_march_hooks.h — instrumentation points of nb_march_fold.hip.  The product build sees them empty.  An experiment build
+// nb_march_hooks.h — instrumentation points of nb_march_fold.hip's kernel (the fix-up, nb_march_fixup.hip, and the stream's
+// packer, nb_march_pack.hip, have none).  The product build sees them empty.  An experiment build
 // pre-includes tools/experiments/fold_instrument.h (hipcc -include ...), which defines them first: cycle stamps at the phase
 // boundaries of a depth step (tools/experiments/fold_phase_times.py) or per-layer accumulator taps (fold_check.py tap).
 #pragma once

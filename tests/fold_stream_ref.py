@@ -1,5 +1,5 @@
-"""A numpy decoder of the f16f6 weight stream (nb_pack_fold_kernel, csrc/nb_march_fold.hip) and the reference quantisers of its
-cross terms.  CPU only; nothing here touches the library.
+"""A numpy decoder of the f16f6 weight stream (nb_pack_fold_kernel, csrc/nb_march_pack.hip; layout: csrc/nb_pack_layout.h) and the
+reference quantisers of its cross terms.  CPU only; nothing here touches the library.
 
 The stream is what the march's four waves read per depth step: per wave 132 one-KiB pieces (64 lanes x 16 bytes) and, behind them,
 14 scale dwords per lane.  A phase (fc_1, fc_2, the folded colour head over the hidden units, the colour head over the encodings) is

@@ -73,6 +73,27 @@ def test_ill_scratch_constants_match_the_header(tmp_path):
     assert abs(float(got[2]) - _lib.ILL_SIGMA) < 1e-9 and abs(float(got[3]) - _lib.ILL_T_MIN) < 1e-12
 
 
+def test_pack_layout_header_matches_the_stream_decoder(tmp_path):
+    """csrc/nb_pack_layout.h, compiled on its own by a host compiler, gives the numbers tests/fold_stream_ref.py restates."""
+    import shutil
+    import subprocess
+
+    from tests import fold_stream_ref as ref
+
+    gxx = shutil.which("g++")
+    assert gxx, "g++ is part of the image"
+    src = tmp_path / "pack_layout.cc"
+    src.write_text('#include <cstdio>\n#include "nb_pack_layout.h"\nusing namespace nbm;\n'
+                   'int main() { std::printf("%d %d %d %d %d %d %d %d %lld %lld\\n", PACK_SIZE, P_TOTAL, N_SCALE, WAVE_STREAM, '
+                   'P_L1, P_L2, P_VG, P_VP, STREAM_FLOATS, BLOB_FLOATS); return 0; }\n')
+    exe = tmp_path / "pack_layout"
+    subprocess.check_call([gxx, "-std=c++17", "-I", build.CSRC, str(src), "-o", str(exe)])
+    got = [int(v) for v in subprocess.check_output([str(exe)]).split()]
+    assert got[:4] == [ref.PACK_F32, ref.P_TOTAL, ref.N_SCALE, ref.WAVE_STREAM], got
+    assert got[4:8] == list(ref.PHASE_P0[:4]) and ref.PHASE_P0[4] == ref.P_TOTAL, got
+    assert got[8:] == [ref.STREAM_FLOATS, ref.PACK_SIZE], got
+
+
 def test_error_codes_without_touching_a_device(lib):
     # NULL scene -> NB_EINVAL and a message, no crash, no launch
     rc = lib.nb_march(None, None, None, None, None, None, None, 10, 64, None, None, None, 0, None, 0, None, None, None,
