@@ -12,6 +12,7 @@
 #include <stdlib.h>
 
 #include "nb_march_common.h"
+#include "nb_tile_out.h"
 #include "nb_trread.h"
 
 using namespace nbm;
@@ -170,8 +171,6 @@ __global__ void trilinear_bwd_kernel(TriArgs a) {
 // tile for it (1.8 ms per GEMM measured).  Split the row range instead: every wave owns (a 256-row chunk, a 32x32 tile
 // of C), accumulates it with v_mfma_f32_32x32x2_f32 (one row pair per MFMA) and adds it to C with fp32 atomics.
 constexpr int TN_ROWS = 256;
-typedef float f32x16_ __attribute__((ext_vector_type(16)));
-__host__ __device__ constexpr int tn_tile_row(int r, int hi) { return (r & 3) + 8 * (r >> 2) + 4 * hi; }
 
 #ifndef NB_TN_WAVES
 #define NB_TN_WAVES 4
@@ -188,9 +187,7 @@ __global__ __launch_bounds__(64 * TN_WAVES) void gemm_tn_kernel(const float *__r
     const long long row0 = ((long long)blockIdx.x * TN_WAVES + wv) * TN_ROWS;
     const int am = blockIdx.y * 32 + i, bn = blockIdx.z * 32 + i;
     const bool aok = am < M, bok = bn < N;
-    f32x16_ acc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+    f32x16 acc = zero_acc();
     if (row0 < R) {  // wave-uniform
 #pragma unroll 8
         for (int m = 0; m < TN_ROWS / 2; ++m) {
@@ -198,27 +195,26 @@ __global__ __launch_bounds__(64 * TN_WAVES) void gemm_tn_kernel(const float *__r
             const bool rok = row < R;
             const float a = (rok && aok) ? A[row * lda + am] : 0.f;
             const float b = (rok && bok) ? B[row * ldb + bn] : 0.f;
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, acc, 0, 0, 0);
+            acc = NB_MFMA(a, b, acc);
         }
     }
 #pragma unroll
     for (int r = 0; r < 16; ++r) red[wv][r][lane] = acc[r];
     __syncthreads();
-    if (bok) {
+    // wave wv sends registers [16 / TN_WAVES * wv, + 16 / TN_WAVES) of the summed tile
+    auto summed = [&](int r) {
+        float v = 0.f;
 #pragma unroll
-        for (int q = 0; q < 16 / TN_WAVES; ++q) {
-            const int r = (16 / TN_WAVES) * wv + q;
-            float v = 0.f;
-#pragma unroll
-            for (int w = 0; w < TN_WAVES; ++w) v += red[w][r][lane];
-            const int cm = blockIdx.y * 32 + tn_tile_row(r, hi);
-            if (cm < M) atomicAdd(&C[(size_t)cm * ldc + bn], alpha * v);
-        }
-    }
+        for (int w = 0; w < TN_WAVES; ++w) v += red[w][r][lane];
+        return v;
+    };
+    nbto::tile_atomic_add_regs<16 / TN_WAVES>(summed, (16 / TN_WAVES) * wv, C, ldc, blockIdx.y * 32, bn, M, bok, alpha);
 }
 
 // The same product on the 16-bit matrix pipe: both operands as bf16 head + remainder (three products per K = 16 chunk, fp32
-// accumulate, ~2^-16 relative), the recipe of conv_bwd_w16_kernel (nb_encoder_bwd.hip): the reduction runs over ROWS, so both
+// accumulate, ~2^-16 relative), the recipe of conv_bwd_w16_kernel (nb_encoder_bwd.hip).  (Its own copy of that recipe and of
+// nbto::tile_atomic_add: on shared pieces the kernel compiles to other code and measured 1 - 4 % slower,
+// profiles/backward_tile_refactor.md.)  The reduction runs over ROWS, so both
 // MFMA operands are K-major; a workgroup stages 32 rows x 128 columns of A and of B row-major in LDS (fp32 -> bf16 pairs on
 // the way) and reads the fragments with ds_read_b64_tr_b16 (nb_trread.h).  One workgroup = a 128 x 128 tile of C over
 // TN16_ROWS rows, wave w a 2 x 2 block of its 32 x 32 tiles; the next chunk's loads are issued before the current chunk's
@@ -280,13 +276,11 @@ __global__ __launch_bounds__(256, 2) void gemm_tn16_kernel(const float *__restri
         stash_one(lds + buf * TN16_BUF, ra);
         stash_one(lds + buf * TN16_BUF + 2 * TN16_PLANE, rb);
     };
-    f32x16_ acc[2][2];
+    f32x16 acc[2][2];
 #pragma unroll
     for (int a = 0; a < 2; ++a)
 #pragma unroll
-        for (int b = 0; b < 2; ++b)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
+        for (int b = 0; b < 2; ++b) acc[a][b] = zero_acc();
     const unsigned lds0 = (unsigned)(size_t)lds, loff = nbtr::lane_offset(lane, TN16_P);
     fetch(0);
     stash(0);
@@ -331,7 +325,7 @@ __global__ __launch_bounds__(256, 2) void gemm_tn16_kernel(const float *__restri
             if (cn >= N) continue;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int cm = m0 + (wm * 2 + a) * 32 + tn_tile_row(r, hi);
+                const int cm = m0 + (wm * 2 + a) * 32 + tile_row(r, hi);
                 if (cm < M) atomicAdd(&C[(size_t)cm * ldc + cn], alpha * acc[a][b][r]);
             }
         }
@@ -347,16 +341,15 @@ __global__ void scale_matrix_kernel(float *__restrict__ C, int m, int n, int ldc
 // ------------------------------------------------------------------ C[R,N] = alpha A[R,K] op(B) + beta C, R large, K and N small
 // (dX = dY.W of the MLP backward: R = rays x samples rows, K, N <= 384).  One wave = 32 rows x up to 4 column tiles of 32;
 // v_mfma_f32_32x32x2_f32 (exact fp32): A operand = one float per lane (row lane % 32, k = 2 c + lane / 32), B operand = the
-// weight element (k, column), C/D in the standard 32x32 layout.  Fused epilogues of the backward chain:
+// weight element (k, column), C/D in the standard 32x32 layout.  Fused epilogues of the backward chain, nbto::rows_epilogue, the
+// way out of all three gemm_rows* kernels:
 //   mask_y   : C *= (Y[row, col] > 0)   — the ReLU that followed the layer whose input gradient this is
 //   colsum   : colsum[col] += sum_rows C (after the mask) — the bias gradient of that layer
 __global__ __launch_bounds__(256, 2) void gemm_rows_kernel(const float *__restrict__ A, int lda, const float *__restrict__ B, int ldb,
                                                         int trans_b, long long R, int K, int N, float alpha, float beta,
                                                         float *__restrict__ C, int ldc, const float *__restrict__ mask_y, int ldy,
                                                         float *__restrict__ colsum) {
-    // column sums: one fp32 atomic per column per WORKGROUP (LDS reduction over the four waves first) — one per wave made
-    // 4096 atomics per address per product and dominated the kernel
-    __shared__ float cs_lds[128];
+    __shared__ float cs_lds[128];  // the column sums of the four waves (rows_epilogue)
     if (threadIdx.x < 128) cs_lds[threadIdx.x] = 0.f;
     __syncthreads();
     const int lane = threadIdx.x & 63, i = lane & 31, kk = lane >> 5;
@@ -365,11 +358,9 @@ __global__ __launch_bounds__(256, 2) void gemm_rows_kernel(const float *__restri
     const long long arow = row0 + i;
     const bool rok = arow < R;
     const float *ap = A + (rok ? arow : 0) * lda;
-    f32x16_ acc[4];
+    f32x16 acc[4];
 #pragma unroll
-    for (int t = 0; t < 4; ++t)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
+    for (int t = 0; t < 4; ++t) acc[t] = zero_acc();
     const int nt = row0 < R ? min(4, (N - col0 + 31) / 32) : 0;  // wave-uniform
     for (int k = 0; k < K && nt > 0; k += 2) {
         const int ke = k + kk;
@@ -381,33 +372,11 @@ __global__ __launch_bounds__(256, 2) void gemm_rows_kernel(const float *__restri
                 const int col = col0 + 32 * t + i;
                 float b = 0.f;
                 if (kok && col < N) b = trans_b ? B[(size_t)col * ldb + ke] : B[(size_t)ke * ldb + col];
-                acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, acc[t], 0, 0, 0);
+                acc[t] = NB_MFMA(a, b, acc[t]);
             }
         }
     }
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-        if (t >= nt) continue;
-        const int col = col0 + 32 * t + i;
-        if (col >= N) continue;
-        float cs = 0.f;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const long long row = row0 + tn_tile_row(r, kk);
-            if (row >= R) continue;
-            float v = alpha * acc[t][r];
-            float *cp = C + row * ldc + col;
-            if (beta != 0.f) v += beta * *cp;
-            if (mask_y && !(mask_y[row * ldy + col] > 0.f)) v = 0.f;
-            *cp = v;
-            cs += v;
-        }
-        if (colsum) atomicAdd(&cs_lds[32 * t + i], cs);
-    }
-    if (colsum) {
-        __syncthreads();
-        if (threadIdx.x < 128 && col0 + (int)threadIdx.x < N) atomicAdd(&colsum[col0 + threadIdx.x], cs_lds[threadIdx.x]);
-    }
+    nbto::rows_epilogue(acc, row0, col0, R, N, alpha, beta, C, ldc, mask_y, ldy, colsum, cs_lds);  // (a tile t >= nt lies beyond N)
 }
 
 // fast path of gemm_rows_kernel (K a multiple of 16, 16-byte aligned operands): a 128-row x 128-column block per workgroup.
@@ -429,11 +398,9 @@ __global__ __launch_bounds__(256, 2) void gemm_rows_fast_kernel(const float *__r
     const int col0 = blockIdx.y * 128;
     const long long arow = min(row0 + i, R - 1);  // rows past the end compute values that are never stored
     const float *ap = A + arow * lda;
-    f32x16_ acc[4];
+    f32x16 acc[4];
 #pragma unroll
-    for (int t = 0; t < 4; ++t)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
+    for (int t = 0; t < 4; ++t) acc[t] = zero_acc();
     // cooperative load of one B chunk: 16 x 128 floats = 512 float4, two per thread
     f32x4 breg[2];
     auto load_b = [&](int k0) {
@@ -490,41 +457,21 @@ __global__ __launch_bounds__(256, 2) void gemm_rows_fast_kernel(const float *__r
             const float av = (c & 1) ? (kk ? q.w : q.z) : (kk ? q.y : q.x);
             const float *bp = &bs[buf][(2 * c + kk) * LDB + i];
 #pragma unroll
-            for (int t = 0; t < 4; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bp[32 * t], acc[t], 0, 0, 0);
+            for (int t = 0; t < 4; ++t) acc[t] = NB_MFMA(av, bp[32 * t], acc[t]);
         }
         if (ch + 1 < nchunk) store_b(buf ^ 1);
 #pragma unroll
         for (int c = 0; c < 4; ++c) a[c] = an[c];
         __syncthreads();
     }
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-        const int col = col0 + 32 * t + i;
-        if (col >= N || row0 >= R) continue;
-        float cs = 0.f;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const long long row = row0 + tn_tile_row(r, kk);
-            if (row >= R) continue;
-            float v = alpha * acc[t][r];
-            float *cp = C + row * ldc + col;
-            if (beta != 0.f) v += beta * *cp;
-            if (mask_y && !(mask_y[row * ldy + col] > 0.f)) v = 0.f;
-            *cp = v;
-            cs += v;
-        }
-        if (colsum) atomicAdd(&cs_lds[32 * t + i], cs);
-    }
-    if (colsum) {
-        __syncthreads();
-        if (threadIdx.x < 128 && col0 + (int)threadIdx.x < N) atomicAdd(&colsum[col0 + threadIdx.x], cs_lds[threadIdx.x]);
-    }
+    nbto::rows_epilogue(acc, row0, col0, R, N, alpha, beta, C, ldc, mask_y, ldy, colsum, cs_lds);
 }
 
 // gemm_rows_fast_kernel (op(B) = B) on the 16-bit matrix pipe, both operands as bf16 head + remainder pairs: the `dX = dY . W`
 // products of the MLP backward.  A fragment: a lane's row, 8 consecutive K values = two float4 straight from global memory, split
 // in registers.  B fragment: K-major (8 consecutive K of one column) from a [32 K][128 columns] LDS tile of bf16 pairs by
-// ds_read_b64_tr_b16 (nb_trread.h), staged once per workgroup and K chunk.  Same tile, same fused epilogue as the fp32 kernel.
+// ds_read_b64_tr_b16 (nb_trread.h), staged once per workgroup and K chunk.  Same tile, same fused epilogue as the fp32 kernel.  (Its own copy of
+// nbto::rows_epilogue: with the shared one the kernel compiles to other code and measured 1 - 4 % slower.)
 __global__ __launch_bounds__(256, 2) void gemm_rows16_kernel(const float *__restrict__ A, int lda, const float *__restrict__ B, int ldb,
                                                           long long R, int K, int N, float alpha, float beta, float *__restrict__ C,
                                                           int ldc, const float *__restrict__ mask_y, int ldy,
@@ -538,11 +485,9 @@ __global__ __launch_bounds__(256, 2) void gemm_rows16_kernel(const float *__rest
     const int col0 = blockIdx.y * 128;
     const long long arow = min(row0 + i, R - 1);  // rows past the end compute values that are never stored
     const float *ap = A + arow * lda;
-    f32x16_ acc[4];
+    f32x16 acc[4];
 #pragma unroll
-    for (int t = 0; t < 4; ++t)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
+    for (int t = 0; t < 4; ++t) acc[t] = zero_acc();
     // cooperative load of one B chunk: 32 x 128 floats: thread -> (k = tid / 8, 16 consecutive columns)
     const int sr = tid >> 3, sp = tid & 7;
     f32x4 breg[4];
@@ -633,7 +578,7 @@ __global__ __launch_bounds__(256, 2) void gemm_rows16_kernel(const float *__rest
         float cs = 0.f;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const long long row = row0 + tn_tile_row(r, kk);
+            const long long row = row0 + tile_row(r, kk);
             if (row >= R) continue;
             float v = alpha * acc[t][r];
             float *cp = C + row * ldc + col;

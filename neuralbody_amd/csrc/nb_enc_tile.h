@@ -2,19 +2,15 @@
 // channel pairs their dispatchers walk): the 32-row MFMA tile and its fragments, the spconv index rule, a tile's prologue, the split
 // (head / remainder) row loads and the BatchNorm sums' way out.
 #pragma once
-#include <hip/hip_runtime.h>
+#include "nb_tile32.h"
 
 // the (Cin, Cout) pairs of SparseConvNet's layers.  The 16-bit forward kernels also run each pair's backward-input convolution
 // (Cout -> Cin) and leave out the pairs with a 16-channel side; the 16-bit weight gradient leaves out Cin = 16.
 #define NB_FOR_CONV_SHAPES(X) X(16, 16) X(16, 32) X(32, 32) X(32, 64) X(64, 64) X(64, 128) X(128, 128)
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef _Float16 bf16x8 __attribute__((ext_vector_type(8)));  // 8 fp16 — or the bits of 8 bf16 (the name predates the switch to fp16)
 typedef _Float16 nb_h16;
 typedef __bf16 nb_bf16x8 __attribute__((ext_vector_type(8)));
-
-#define NB_MFMA(a, b, c) __builtin_amdgcn_mfma_f32_32x32x2f32((a), (b), (c), 0, 0, 0)
 
 // BF: the operands are bf16 head / remainder pairs (the backward-input convolution: gradients span more binades than an
 // un-scaled fp16 head holds; a bf16 pair carries 16 mantissa bits, ~2^-16 relative per product) instead of fp16 pairs
@@ -32,16 +28,6 @@ namespace {
 struct Dims {
     int d, h, w;
 };
-
-// row of a 32x32 D fragment that accumulator register r of a lane of half hi holds
-__host__ __device__ constexpr int tile_row(int r, int hi) { return (r & 3) + 8 * (r >> 2) + 4 * hi; }
-
-__device__ __forceinline__ f32x16 zero_acc() {
-    f32x16 a;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) a[r] = 0.f;
-    return a;
-}
 
 __device__ __forceinline__ bf16x8 zero_fragment() {
     bf16x8 z;

@@ -12,6 +12,7 @@
 //   nb_enc_scatter_codes_bwd  d c.weight[vertex of row r] = d rows[r]  (Embedding lookup backward, :33-34)
 #include "nb_common.h"
 #include "nb_enc_tile.h"
+#include "nb_tile_out.h"
 #include "nb_trread.h"
 
 namespace {
@@ -202,13 +203,7 @@ __global__ __launch_bounds__(256, 2) void conv_bwd_w_kernel(const float *__restr
     }
     if (!__any(any)) return;
     // D fragment: lane (j = co column, hi) holds rows ci_local = tile_row(r, hi)
-    if (cook) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int cir = ti * 32 + tile_row(r, hi);
-            if ((CIN % 32 == 0) || cir < CIN) atomicAdd(&dw[((size_t)o * CIN + cir) * COUT + co], acc[r]);
-        }
-    }
+    nbto::tile_atomic_add<CIN % 32 != 0>(acc, dw + (size_t)o * CIN * COUT, COUT, ti * 32, co, CIN, cook, 1.f);
 }
 
 __global__ void scatter_codes_bwd_kernel(const float *__restrict__ drows, const int *__restrict__ rows_vert,
@@ -232,8 +227,6 @@ __global__ void scatter_codes_bwd_kernel(const float *__restrict__ drows, const 
 // ONE set of atomics (the exact-fp32 kernel: one set per 256 rows), wave w owns a block of the [C_in / 32] x [C_out / 32]
 // tiles.  The next chunk's global loads are issued before the current chunk's MFMAs (two LDS buffers).
 constexpr int BW_ROWS = 1024;
-typedef nbtr::bf8 nb_bf8;
-__device__ __forceinline__ nb_bf8 tr_frag(unsigned addr_lo4, unsigned addr_hi4) { return nbtr::frag(addr_lo4, addr_hi4); }
 
 template <int CIN, int COUT>
 __global__ __launch_bounds__(256, 2) void conv_bwd_w16_kernel(const float *__restrict__ in_rows, const int *__restrict__ nbr,
@@ -285,11 +278,7 @@ __global__ __launch_bounds__(256, 2) void conv_bwd_w16_kernel(const float *__res
             const float v[4] = {ra[q].x, ra[q].y, ra[q].z, ra[q].w};
             unsigned short h[4], l[4];
 #pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const __bf16 hh = (__bf16)v[e];
-                h[e] = __builtin_bit_cast(unsigned short, hh);
-                l[e] = __builtin_bit_cast(unsigned short, (__bf16)(v[e] - (float)hh));
-            }
+            for (int e = 0; e < 4; ++e) nbtr::split_bf16(v[e], h[e], l[e]);
             const int cb = (sp * (CIN / 8) + 4 * q) * 2;
             *reinterpret_cast<uint2 *>(base + sr * PA + cb) = uint2{h[0] | ((unsigned)h[1] << 16), h[2] | ((unsigned)h[3] << 16)};
             *reinterpret_cast<uint2 *>(base + A_BYTES + sr * PA + cb) = uint2{l[0] | ((unsigned)l[1] << 16), l[2] | ((unsigned)l[3] << 16)};
@@ -309,11 +298,8 @@ __global__ __launch_bounds__(256, 2) void conv_bwd_w16_kernel(const float *__res
     for (int a = 0; a < TCI; ++a)
 #pragma unroll
         for (int b = 0; b < TCO; ++b) acc[a][b] = zero_acc();
-    // fragment addressing: lane l of 16-lane group g addresses segment (row 8 (g >> 1) + (l15 >> 2), channels 16 (g & 1) + 4 (l15 & 3))
-    const int l15 = lane & 15, g = lane >> 4;
     const unsigned lds0 = (unsigned)(size_t)lds;
-    const unsigned a_lane = (8 * (g >> 1) + (l15 >> 2)) * PA + (16 * (g & 1) + 4 * (l15 & 3)) * 2;
-    const unsigned b_lane_off = (8 * (g >> 1) + (l15 >> 2)) * PB + (16 * (g & 1) + 4 * (l15 & 3)) * 2;
+    const unsigned a_off = nbtr::lane_offset(lane, PA), b_off = nbtr::lane_offset(lane, PB);
 
     fetch(0);
     stash(0);
@@ -324,20 +310,22 @@ __global__ __launch_bounds__(256, 2) void conv_bwd_w16_kernel(const float *__res
             const unsigned base = lds0 + (c & 1) * BUF;
 #pragma unroll
             for (int kc = 0; kc < 2; ++kc) {
-                nb_bf8 ah[TCI], al[TCI], bh[TCO], bl[TCO];
+                nbtr::bf8 ah[TCI], al[TCI], bh[TCO], bl[TCO];
 #pragma unroll
                 for (int a = 0; a < TCI; ++a) {
-                    const unsigned ad = base + a_lane + kc * 16 * PA + ((wci * TCI + a) * 32) * 2;
-                    ah[a] = tr_frag(ad, ad + 4 * PA);
-                    al[a] = tr_frag(ad + A_BYTES, ad + A_BYTES + 4 * PA);
+                    const unsigned ad = base + a_off + kc * 16 * PA + ((wci * TCI + a) * 32) * 2;
+                    ah[a] = nbtr::frag(ad, ad + 4 * PA);
+                    al[a] = nbtr::frag(ad + A_BYTES, ad + A_BYTES + 4 * PA);
                 }
 #pragma unroll
                 for (int b = 0; b < TCO; ++b) {
-                    const unsigned bd = base + 2 * A_BYTES + b_lane_off + kc * 16 * PB + ((wco * TCO + b) * 32) * 2;
-                    bh[b] = tr_frag(bd, bd + 4 * PB);
-                    bl[b] = tr_frag(bd + B_BYTES, bd + B_BYTES + 4 * PB);
+                    const unsigned bd = base + 2 * A_BYTES + b_off + kc * 16 * PB + ((wco * TCO + b) * 32) * 2;
+                    bh[b] = nbtr::frag(bd, bd + 4 * PB);
+                    bl[b] = nbtr::frag(bd + B_BYTES, bd + B_BYTES + 4 * PB);
                 }
-                // the reads above are inline asm: the compiler does not count them, so the wait is tied to every fragment register
+                // nbtr::frag is a compiler builtin: the compiler counts its reads and would wait in front of each fragment's first consumer.
+                // ONE wait tied to every fragment register instead keeps all the reads of the half-chunk ahead of it and its MFMAs
+                // behind it, back to back (an ordering device, not a correctness one; an asm operand list cannot expand a pack)
                 if constexpr (TCI == 2 && TCO == 2)
                     asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(ah[0]), "+v"(al[0]), "+v"(ah[1]), "+v"(al[1]), "+v"(bh[0]), "+v"(bl[0]), "+v"(bh[1]), "+v"(bl[1]));
                 else if constexpr (TCI == 1 && TCO == 2)
@@ -361,18 +349,11 @@ __global__ __launch_bounds__(256, 2) void conv_bwd_w16_kernel(const float *__res
     }
     if (!active) return;
     // D fragment: lane (j = output channel, hi) holds input channels tile_row(r, hi)
-    const int j = lane & 31, hi = lane >> 5;
 #pragma unroll
     for (int a = 0; a < TCI; ++a)
 #pragma unroll
-        for (int b = 0; b < TCO; ++b) {
-            const int co = (wco * TCO + b) * 32 + j;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int ci = (wci * TCI + a) * 32 + tile_row(r, hi);
-                atomicAdd(&dw[((size_t)o * CIN + ci) * COUT + co], acc[a][b][r]);
-            }
-        }
+        for (int b = 0; b < TCO; ++b)
+            nbto::tile_atomic_add<false>(acc[a][b], dw + (size_t)o * CIN * COUT, COUT, (wci * TCI + a) * 32, (wco * TCO + b) * 32 + (lane & 31), CIN, true, 1.f);
 }
 
 // bf16 pairs of dx given: the matrix-pipe kernel (the 16-channel layers stay exact fp32)

@@ -31,7 +31,6 @@
 using namespace nbm;
 
 #define NB_PF 8  // weight fragments in flight per wave
-#define NB_MFMA(a, b, c) __builtin_amdgcn_mfma_f32_32x32x2f32((a), (b), (c), 0, 0, 0)
 
 namespace {
 

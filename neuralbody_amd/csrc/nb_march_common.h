@@ -4,9 +4,7 @@
 // positional encoding, sampling helpers, compositing, XCD-aware block remap.
 #pragma once
 #include "nb_common.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+#include "nb_tile32.h"
 
 namespace nbm {
 
@@ -24,9 +22,7 @@ __device__ __forceinline__ float relu1(float x) {
     return r;
 }
 
-// feature row (within a 32-row tile) held by accumulator register r of a lane with half index hi
-__host__ __device__ constexpr int tile_row(int r, int hi) { return (r & 3) + 8 * (r >> 2) + 4 * hi; }
-// ... and its inverse: feature row `row` (0..31) of a tile is register tile_reg(row) of the lanes with half index tile_hi(row)
+// the inverse of tile_row (nb_tile32.h): feature row `row` (0..31) of a tile is register tile_reg(row) of the lanes with half index tile_hi(row)
 __host__ __device__ constexpr int tile_hi(int row) { return (row >> 2) & 1; }
 __host__ __device__ constexpr int tile_reg(int row) { return (row & 3) + 4 * (row >> 3); }
 constexpr bool tile_row_round_trip() {
