@@ -223,7 +223,7 @@ __global__ __launch_bounds__(256) void nb_march_kernel(MarchArgs a) {
     const float ox = a.ray_o[ray * 3 + 0], oy = a.ray_o[ray * 3 + 1], oz = a.ray_o[ray * 3 + 2];
     const float dx = a.ray_d[ray * 3 + 0], dy = a.ray_d[ray * 3 + 1], dz = a.ray_d[ray * 3 + 2];
     const float near = a.near[ray], far = a.far[ray];
-    const float dn = sqrtf(__fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz)));
+    const float dn = ray_norm(dx, dy, dz);
     const float vx = dx / dn, vy = dy / dn, vz = dz / dn;  // if_clight_renderer.py:68
     float pe[N_PE];
     pe_view(pe, vx, vy, vz, hi);
@@ -235,7 +235,7 @@ __global__ __launch_bounds__(256) void nb_march_kernel(MarchArgs a) {
         // stratified jitter (if_clight_renderer.py:16-23)
         const float lower = s == 0 ? zc : 0.5f * __fadd_rn(zc, z_lin(near, far, a.t_vals[s - 1]));
         const float upper = s == S - 1 ? zc : 0.5f * __fadd_rn(z_lin(near, far, a.t_vals[s + 1]), zc);
-        return __fadd_rn(lower, __fmul_rn(__fsub_rn(upper, lower), tr[s]));
+        return z_jitter(lower, upper, tr[s]);
     };
 
     RayAccum ra;
@@ -243,9 +243,9 @@ __global__ __launch_bounds__(256) void nb_march_kernel(MarchArgs a) {
     float z_cur = z_at(0);
     for (int s = 0; s < S; ++s) {
         const float z_next = (s + 1 < S) ? z_at(s + 1) : 0.f;
-        const float px = __fadd_rn(ox, __fmul_rn(dx, z_cur));
-        const float py = __fadd_rn(oy, __fmul_rn(dy, z_cur));
-        const float pz = __fadd_rn(oz, __fmul_rn(dz, z_cur));
+        const float px = ray_point(ox, dx, z_cur);
+        const float py = ray_point(oy, dy, z_cur);
+        const float pz = ray_point(oz, dz, z_cur);
         pe_xyz(pe, px, py, pz, vx, vy, vz, hi);
         float out[4];
         // the weight stream is loop-invariant: hide the base pointers from LICM, which would otherwise
@@ -281,7 +281,7 @@ __global__ __launch_bounds__(256) void nb_composite_kernel(const float *__restri
     const long long ray = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (ray >= n_rays) return;
     const float dx = ray_d[ray * 3], dy = ray_d[ray * 3 + 1], dz = ray_d[ray * 3 + 2];
-    const float dn = sqrtf(__fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz)));
+    const float dn = ray_norm(dx, dy, dz);
     float T = 1.f, cr = 0.f, cg = 0.f, cb = 0.f, depth = 0.f, accw = 0.f;
     for (int base = 0; base < S; base += 64) {
         const int s = base + lane;

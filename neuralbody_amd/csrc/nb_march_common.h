@@ -495,9 +495,28 @@ __device__ __forceinline__ int xcd_remap(int b, int n) {
     return full + (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + i;
 }
 
+// ---------------------------------------------------------------- sampling: the steps the reference rounds one operation at a time
+// The `_rn` device intrinsics of this toolchain are the plain operators, and hipcc contracts a * b + c into an FMA across inlined
+// calls (__fadd_rn(o, __fmul_rn(d, z)) assembles to v_fmac_f32).  Sample depths, the jitter, sample positions and |d| are therefore
+// written with plain operators under a contraction pragma of their own: the instructions keep it wherever they are inlined, so each
+// is ONE IEEE operation, as in torch (tests/test_gpu_march_rays.py holds the march to numpy float32 restatements of them, bit for bit).
 __device__ __forceinline__ float z_lin(float near, float far, float t) {
-    // near * (1 - t) + far * t   (if_clight_renderer.py:14), no contraction
-    return __fadd_rn(__fmul_rn(near, __fsub_rn(1.f, t)), __fmul_rn(far, t));
+#pragma clang fp contract(off)
+    return near * (1.f - t) + far * t;  // if_clight_renderer.py:14
+}
+// lower + (upper - lower) * t_rand   (if_clight_renderer.py:23)
+__device__ __forceinline__ float z_jitter(float lower, float upper, float t) {
+#pragma clang fp contract(off)
+    return lower + (upper - lower) * t;
+}
+// one axis of o + d * z   (if_clight_renderer.py:25)
+__device__ __forceinline__ float ray_point(float o, float d, float z) {
+#pragma clang fp contract(off)
+    return o + d * z;
+}
+__device__ __forceinline__ float ray_norm(float dx, float dy, float dz) {
+#pragma clang fp contract(off)
+    return sqrtf((dx * dx + dy * dy) + dz * dz);
 }
 
 

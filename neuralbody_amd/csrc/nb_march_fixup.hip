@@ -55,9 +55,8 @@ __global__ __launch_bounds__(256) void nb_march_fixup_kernel(MarchArgs a) {
         const float z = rec[4];
         if (tid < 32) {  // (level, corner): weight and U row, with the march's own arithmetic (prep_sequential, wt_build)
             const int L = tid >> 3, corner = tid & 7;
-            const float px = __fadd_rn(a.ray_o[ray * 3 + 0], __fmul_rn(a.ray_d[ray * 3 + 0], z)),
-                        py = __fadd_rn(a.ray_o[ray * 3 + 1], __fmul_rn(a.ray_d[ray * 3 + 1], z)),
-                        pz = __fadd_rn(a.ray_o[ray * 3 + 2], __fmul_rn(a.ray_d[ray * 3 + 2], z));
+            const float px = ray_point(a.ray_o[ray * 3 + 0], a.ray_d[ray * 3 + 0], z), py = ray_point(a.ray_o[ray * 3 + 1], a.ray_d[ray * 3 + 1], z),
+                        pz = ray_point(a.ray_o[ray * 3 + 2], a.ray_d[ray * 3 + 2], z);
             const GridCoord g = grid_coords(a.sc, px, py, pz);
             Lvl lv;
             lv.D = a.sc.dhw[L][0]; lv.H = a.sc.dhw[L][1]; lv.W = a.sc.dhw[L][2];

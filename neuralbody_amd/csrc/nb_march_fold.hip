@@ -915,7 +915,7 @@ __global__ __launch_bounds__(256, 2) void nb_march_fold_kernel(MarchArgs a, cons
             ox = a.ray_o[ray * 3 + 0], oy = a.ray_o[ray * 3 + 1], oz = a.ray_o[ray * 3 + 2];
             dx = a.ray_d[ray * 3 + 0], dy = a.ray_d[ray * 3 + 1], dz = a.ray_d[ray * 3 + 2];
             near = a.near[ray], far = a.far[ray];
-            dn = sqrtf(__fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz)));
+            dn = ray_norm(dx, dy, dz);
             vx = dx / dn, vy = dy / dn, vz = dz / dn;
         }
         if ((lane >> 4) == 0) {
@@ -936,7 +936,7 @@ __global__ __launch_bounds__(256, 2) void nb_march_fold_kernel(MarchArgs a, cons
         if (!tr) return zc;
         const float lower = s == 0 ? zc : 0.5f * __fadd_rn(zc, z_lin(near, far, tval(s - 1)));
         const float upper = s == S - 1 ? zc : 0.5f * __fadd_rn(z_lin(near, far, tval(s + 1)), zc);
-        return __fadd_rn(lower, __fmul_rn(__fsub_rn(upper, lower), tr[s]));
+        return z_jitter(lower, upper, tr[s]);
     };
 
     {
@@ -982,8 +982,7 @@ __global__ __launch_bounds__(256, 2) void nb_march_fold_kernel(MarchArgs a, cons
         const f32x4 *rec = reinterpret_cast<const f32x4 *>(lds + RAY_OFF) + sample * (RAY_FLOATS / 4);
         const f32x4 ro = rec[0], rd = rec[1];
         z_out = z_at(sn, ro.w, rd.w);
-        const float px = __fadd_rn(ro.x, __fmul_rn(rd.x, z_out)), py = __fadd_rn(ro.y, __fmul_rn(rd.y, z_out)),
-                    pz = __fadd_rn(ro.z, __fmul_rn(rd.z, z_out));
+        const float px = ray_point(ro.x, rd.x, z_out), py = ray_point(ro.y, rd.y, z_out), pz = ray_point(ro.z, rd.z, z_out);
         g = grid_coords(a.sc, px, py, pz);
         if constexpr (CULL) ins = cull_inside(a.cull, a.sc, px, py, pz);
         const Lvl lv = load_lvl(lds, part);
@@ -1090,8 +1089,7 @@ __global__ __launch_bounds__(256, 2) void nb_march_fold_kernel(MarchArgs a, cons
             Conv6 pec;
             {
                 const f32x4 ro = rec[0], rd = rec[1], rv = rec[2];  // ox oy oz near | dx dy dz far | vx vy vz |d|
-                const float xa = part == 0 ? __fadd_rn(ro.x, __fmul_rn(rd.x, z_cur))
-                                           : (part == 1 ? __fadd_rn(ro.y, __fmul_rn(rd.y, z_cur)) : __fadd_rn(ro.z, __fmul_rn(rd.z, z_cur)));
+                const float xa = part == 0 ? ray_point(ro.x, rd.x, z_cur) : (part == 1 ? ray_point(ro.y, rd.y, z_cur) : ray_point(ro.z, rd.z, z_cur));
                 const float va = part == 0 ? rv.x : (part == 1 ? rv.y : rv.z);
                 Rev2 tx, tv;
                 float e[32];
@@ -1133,8 +1131,7 @@ __global__ __launch_bounds__(256, 2) void nb_march_fold_kernel(MarchArgs a, cons
             if (more) {
                 const f32x4 ro = rec[0], rd = rec[1];
                 z_next = z_at(s + 1, ro.w, rd.w);
-                const float px = __fadd_rn(ro.x, __fmul_rn(rd.x, z_next)), py = __fadd_rn(ro.y, __fmul_rn(rd.y, z_next)),
-                            pz = __fadd_rn(ro.z, __fmul_rn(rd.z, z_next));
+                const float px = ray_point(ro.x, rd.x, z_next), py = ray_point(ro.y, rd.y, z_next), pz = ray_point(ro.z, rd.z, z_next);
                 g = grid_coords(a.sc, px, py, pz);
                 if constexpr (CULL) ins = cull_inside(a.cull, a.sc, px, py, pz);
                 const Lvl lv = load_lvl(actz, part);
