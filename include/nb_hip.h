@@ -770,6 +770,50 @@ int nb_mesh_render_attr(const float *verts, const float *attr, const int32_t *fa
                         void *scratch, int64_t scratch_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------------
+ * Field normals on device — the surface normal of the density field, n(p) = -grad sigma(p) / |grad sigma(p)|, for the samples of
+ * a marched view and for mesh vertices.  replaces: nothing in the reference (it has no normal output; its turntable shades with
+ * the face normals of the marching-cubes mesh, tools/render_mesh.py:21-51).  The decoder part of d sigma / dp is the tap of
+ * nb_decode_points and three nb_gemm_fused products (Network.calculate_density_gradient); these calls are the rest.
+ *   Rules of every call: no allocation, no synchronisation, no atomics, everything on `stream`: the same inputs give the same
+ *   bits.  n == 0 (no point, no sample, no ray) returns NB_OK at once and looks at no pointer.
+ * nb_trilinear_grad — replaces: nothing in the reference.  The coordinate twin of nb_trilinear_bwd: the same scene, the same
+ *   index grids, and rows[l] dev [n_rows_l, C_l] fp32, 16-byte aligned: the ACTIVE rows of level l (scene->vol[] is not read).
+ *   wpts dev [n,3] world points, d_feat dev [n,352] (16-byte aligned) -> grad dev [n,3] out, world axes; 0 <= n < 2^31 - 256, else NB_EINVAL:
+ *       grad[p] = d/dp ( sum_c d_feat[p,c] F_c(p) ),  F the 4-level lookup of latent_xyzc.py:62-72.
+ *   Per level l of size (D, H, W): the index coordinates (ix, iy, iz), the cell (x0, y0, z0) = their floors and the weight pairs
+ *   wx = {x0 + 1 - ix, ix - x0}, wy, wz are the forward gather's, formed by the same device functions; v(dx,dy,dz)[c] is the row
+ *   the grid names for voxel (x0+dx, y0+dy, z0+dz), or 0 for a voxel out of bounds or with grid entry -1.
+ *       t_x = sum_c d_feat[c] sum_{dy,dz} wy[dy] wz[dz] (v(1,dy,dz)[c] - v(0,dy,dz)[c]),   t_y, t_z alike
+ *   (evaluated as sum_{dy,dz} wy wz (p(1,dy,dz) - p(0,dy,dz)) with p(corner) = sum_c d_feat[c] v(corner)[c]).  The gradient of a
+ *   point is that of the cell the forward assigns it: at an integer index coordinate the right-hand derivative.  A level whose
+ *   index coordinate was clamped (outside [-2, size + 1]) contributes 0.  Canonical gradient gc_x = sum_l t_x,l (W_l - 1) /
+ *   (voxel_size[2] out_sh[2]), gc_y with H_l and [1], gc_z with D_l and [0]; world gradient grad_i = sum_j R[i][j] gc_j (canonical
+ *   = (p - Th) @ R).  fp32 throughout.  Eight lanes serve a point (each 16-byte piece of a row is read once), a wave eight
+ *   consecutive points.
+ * nb_normal_select — replaces: nothing in the reference.  Which samples of a marched view get a gradient: every (ray, s) with
+ *   weights[ray, s] >= w_min (a NaN is not selected), in (ray, s) order.  ray_o, ray_d dev [n_rays,3], near, far dev [n_rays],
+ *   t_vals dev [S], t_rand dev [n_rays,S] or NULL, weights dev [n_rays,S] (nb_march's output): the arguments of that march.
+ *   idx dev [cap] int32 out = ray * S + s; wpts dev [cap,3] fp32 out = the sample's position by the march's own steps (z_lin,
+ *   the stratified jitter when t_rand is given, ray_point: bit for bit the point the march decoded); selected samples beyond
+ *   cap are dropped and nothing is written behind row min(total, cap); n_out dev [2] int32 = {min(total, cap), total}.  cap = 0
+ *   only counts (idx, wpts may be NULL): the caller reads these 8 bytes to size the outputs, the capacity rule of
+ *   nb_lattice_gather.  n_rays * S < 2^31 - 256, else NB_EINVAL.  scratch dev: nb_scan_scratch_size(n_rays * S) bytes.
+ * nb_normal_composite — replaces: nothing in the reference.  idx dev [m] int32 ascending (nb_normal_select's), grad dev [m,3]
+ *   fp32 (d sigma / dp of the selected samples), weights dev [n_rays,S] -> normal_map dev [n_rays,3], normal_acc dev [n_rays],
+ *   EVERY ray written.  Per selected sample nhat = -grad (/) |grad|, or 0 when |grad| < 1e-12 or not finite (|grad| =
+ *   sqrt((gx gx (+) gy gy) (+) gz gz) in fp32).  Per ray, over its selected samples in sample order, one IEEE operation per step,
+ *   none contracted: sum = sum (+) w_s (*) nhat_s per axis, normal_acc = sum_s w_s (every selected sample, also one without a
+ *   direction); normal_map = sum (/) |sum|, or (0, 0, 0) when |sum| < 1e-6 or not finite.  A thread per ray finds its run in idx
+ *   by bisection.  0 <= m <= n_rays * S < 2^31 - 256, else NB_EINVAL. */
+int nb_trilinear_grad(const nb_scene *scene, const int32_t *const grids[4], const float *const rows[4], const float *wpts,
+                      const float *d_feat, int64_t n, float *grad, void *stream);
+int nb_normal_select(const float *ray_o, const float *ray_d, const float *near, const float *far, int64_t n_rays, int32_t n_samples,
+                     const float *t_vals, const float *t_rand, const float *weights, float w_min, int32_t cap, int32_t *idx,
+                     float *wpts, int32_t *n_out, void *scratch, void *stream);
+int nb_normal_composite(const int32_t *idx, const float *grad, int64_t m, const float *weights, int64_t n_rays, int32_t n_samples,
+                        float *normal_map, float *normal_acc, void *stream);
+
+/* ---------------------------------------------------------------------------------
  * A photographed frame on device — replaces the OpenCV calls between the image files and the kernels above:
  * lib/datasets/light_stage/multi_view_dataset.py:58-64 (get_mask: cv2.erode, cv2.dilate, the border band), :129-142 (cv2.undistort
  * of the float32 image and the uint8 mask, cv2.resize INTER_AREA / INTER_NEAREST by cfg.ratio, the background fill) and

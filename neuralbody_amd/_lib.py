@@ -150,6 +150,9 @@ SIGNATURES = {
     "nb_mesh_color_query": (C.c_int, [_P, _P, _P, _P, C.c_float, _I32, _P, _P, _P]),
     "nb_mesh_color_finish": (C.c_int, [_P, _I32, _P, _P, _P]),
     "nb_mesh_render_attr": (C.c_int, [_P, _P, _P, _I32, _I32, _P, _I32, _I32, _I32, _P, _P, _P, _P, _I64, _P]),
+    "nb_trilinear_grad": (C.c_int, [C.POINTER(NbScene), C.c_void_p * 4, C.c_void_p * 4, _P, _P, _I64, _P, _P]),
+    "nb_normal_select": (C.c_int, [_P, _P, _P, _P, _I64, _I32, _P, _P, _P, C.c_float, _I32, _P, _P, _P, _P, _P]),
+    "nb_normal_composite": (C.c_int, [_P, _P, _I64, _P, _I64, _I32, _P, _P, _P]),
     "nb_mask_band": (C.c_int, [_P, _I32, _I32, _I32, _I32, _P, _P]),
     "nb_image_undistort": (C.c_int, [_P, _P, C.POINTER(C.c_double), _I32, _I32, _I32, _I32, C.c_int, _P, _P, _P]),
 }

@@ -372,6 +372,18 @@ __device__ __forceinline__ float unnorm_clamped(float gcoord, int size) {
     return fminf(fmaxf(i, -2.f), (float)size + 1.f);
 }
 
+// One axis of a level's cell: the floor of the (clamped) index coordinate and the weight pair of its two voxel planes, as
+// gather_level and gather_level_coop form them (they keep their own lines: their code is held bit for bit by the march's tests and
+// is not rebuilt for this helper's sake).  For code beside the march that needs the forward's cell: nb_field_normal.hip.
+struct AxisCell {
+    int i0;      // floor(i): the cell; at an integer coordinate the one to the right
+    float w[2];  // {i0 + 1 - i, i - i0}
+};
+__device__ __forceinline__ AxisCell cell_weights(float i) {
+    const float f = floorf(i);
+    return {(int)f, {(f + 1.f) - i, i - f}};
+}
+
 template <int L, int BUF_BYTES>
 __device__ __forceinline__ void gather_level_coop(const SceneDev &sc, const GridCoord &g, const WaveBox &wb, int hi,
                                                   int lane, char *buf, float (&out)[lvl_c(L) / 2]) {
@@ -513,6 +525,16 @@ __device__ __forceinline__ float z_jitter(float lower, float upper, float t) {
 __device__ __forceinline__ float ray_point(float o, float d, float z) {
 #pragma clang fp contract(off)
     return o + d * z;
+}
+// The depth of sample s of S along a ray: z_lin, then the stratified jitter when the ray has a row `tr` of t_rand
+// (if_clight_renderer.py:16-23) — the `z_at` of the two march kernels (which keep their own lambdas, for the reason given at
+// cell_weights) for code beside the march that needs the position the march decoded: nb_field_normal.hip.
+__device__ __forceinline__ float z_sample(float near, float far, const float *t_vals, const float *tr, int s, int S) {
+    const float zc = z_lin(near, far, t_vals[s]);
+    if (!tr) return zc;
+    const float lower = s == 0 ? zc : 0.5f * __fadd_rn(zc, z_lin(near, far, t_vals[s - 1]));
+    const float upper = s == S - 1 ? zc : 0.5f * __fadd_rn(z_lin(near, far, t_vals[s + 1]), zc);
+    return z_jitter(lower, upper, tr[s]);
 }
 __device__ __forceinline__ float ray_norm(float dx, float dy, float dz) {
 #pragma clang fp contract(off)

@@ -5,7 +5,7 @@ import numpy as np
 
 
 class TriMesh:
-    def __init__(self, vertices, faces, vertex_colors=None):
+    def __init__(self, vertices, faces, vertex_colors=None, vertex_normals=None):
         self.vertices = np.ascontiguousarray(vertices, dtype=np.float64).reshape(-1, 3)
         self.faces = np.ascontiguousarray(faces, dtype=np.int64).reshape(-1, 3)
         self.vertex_colors = None  # uint8 [V,3] RGB, or None: a mesh without colours
@@ -14,11 +14,17 @@ class TriMesh:
             if colors.dtype != np.uint8 or colors.shape != (len(self.vertices), 3):
                 raise ValueError("vertex_colors must be uint8 [%d,3], got %s %s" % (len(self.vertices), colors.dtype, colors.shape))
             self.vertex_colors = np.ascontiguousarray(colors)
+        self.vertex_normals = None  # float32 [V,3], or None: a mesh without normals of its own (cfg.mesh_normals: field gives them)
+        if vertex_normals is not None:
+            normals = np.asarray(vertex_normals)
+            if normals.dtype.kind != "f" or normals.shape != (len(self.vertices), 3):
+                raise ValueError("vertex_normals must be float [%d,3], got %s %s" % (len(self.vertices), normals.dtype, normals.shape))
+            self.vertex_normals = np.ascontiguousarray(normals, dtype=np.float32)
 
     def export(self, path):
         r"""Binary little-endian PLY: float32 vertices, triangles as `list uchar int` (what trimesh writes for a `.ply` path); with
         vertex_colors, `property uchar red / green / blue` behind x y z (what trimesh writes for a coloured mesh, without alpha).
-        Without colours the header is
+        With vertex_normals, `property float nx / ny / nz` between the two (trimesh's order).  Without either the header is
             "ply\nformat binary_little_endian 1.0\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\n"
             "element face %d\nproperty list uchar int vertex_indices\nend_header\n" % (V, T)
         followed by V x 3 little-endian float32 and T records of (uchar 3, 3 little-endian int32)."""
@@ -27,18 +33,25 @@ class TriMesh:
             raise ValueError("TriMesh.export writes PLY only (got %r); install trimesh for other formats" % path)
         nv, nf = len(self.vertices), len(self.faces)
         colors = "" if self.vertex_colors is None else "property uchar red\nproperty uchar green\nproperty uchar blue\n"
-        header = ("ply\nformat binary_little_endian 1.0\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\n%s"
-                  "element face %d\nproperty list uchar int vertex_indices\nend_header\n" % (nv, colors, nf))
+        normals = "" if self.vertex_normals is None else "property float nx\nproperty float ny\nproperty float nz\n"
+        header = ("ply\nformat binary_little_endian 1.0\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\n%s%s"
+                  "element face %d\nproperty list uchar int vertex_indices\nend_header\n" % (nv, normals, colors, nf))
         faces = np.empty(nf, dtype=[("n", "u1"), ("v", "<i4", (3,))])
         faces["n"] = 3
         faces["v"] = self.faces
         with open(path, "wb") as f:
             f.write(header.encode("ascii"))
-            if self.vertex_colors is None:
+            if self.vertex_colors is None and self.vertex_normals is None:
                 f.write(self.vertices.astype("<f4").tobytes())
             else:
-                verts = np.empty(nv, dtype=[("p", "<f4", (3,)), ("c", "u1", (3,))])
-                verts["p"], verts["c"] = self.vertices, self.vertex_colors
+                fields = [("p", "<f4", (3,))] + ([] if self.vertex_normals is None else [("n", "<f4", (3,))]) + \
+                    ([] if self.vertex_colors is None else [("c", "u1", (3,))])
+                verts = np.empty(nv, dtype=fields)
+                verts["p"] = self.vertices
+                if self.vertex_normals is not None:
+                    verts["n"] = self.vertex_normals
+                if self.vertex_colors is not None:
+                    verts["c"] = self.vertex_colors
                 f.write(verts.tobytes())
             f.write(faces.tobytes())
         return path
@@ -50,7 +63,8 @@ class TriMesh:
     @classmethod
     def load_ply(cls, path):
         """Reads what `export` and trimesh write: binary little-endian PLY, a vertex element with float or double x / y / z
-        (uchar red / green / blue, when all three are there, come back as vertex_colors; further scalar properties are skipped), then
+        (uchar red / green / blue, when all three are there, come back as vertex_colors, float nx / ny / nz as vertex_normals; further
+        scalar properties are skipped), then
         a face element of `list uchar int|uint` triangles.  Anything else is
         refused with what was found."""
         with open(str(path), "rb") as f:
@@ -93,4 +107,7 @@ class TriMesh:
         colors = None
         if all(k in vdtype.names and vdtype[k] == np.uint8 for k in ("red", "green", "blue")):
             colors = np.stack([verts["red"], verts["green"], verts["blue"]], 1)
-        return cls(np.stack([verts["x"], verts["y"], verts["z"]], 1), faces["v"], colors)
+        normals = None
+        if all(k in vdtype.names and vdtype[k].kind == "f" for k in ("nx", "ny", "nz")):
+            normals = np.stack([verts["nx"], verts["ny"], verts["nz"]], 1).astype(np.float32)
+        return cls(np.stack([verts["x"], verts["y"], verts["z"]], 1), faces["v"], colors, normals)

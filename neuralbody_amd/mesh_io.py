@@ -62,10 +62,16 @@ class MeshVisualizer:
 
     def render_turntable(self, mesh, directory, colors=False):
         """tools/render_mesh.py on the mesh just written: the 91 normal-shaded views as `directory/%d.jpg`, drawn on the device
-        (neuralbody_amd/mesh_render.py) -> the paths.  colors: the views in the mesh's vertex colours instead."""
+        (neuralbody_amd/mesh_render.py) -> the paths.  colors: the views in the mesh's vertex colours instead.  This package's own
+        TriMesh with vertex_normals (cfg.mesh_normals: field) is shaded with those; every other mesh — a trimesh.Trimesh, whose
+        `vertex_normals` property is trimesh's own estimate, included — with the triangles' own (nb_mesh_vertex_normals), as before."""
+        from .mesh import TriMesh
         from .mesh_render import MeshTurntable
 
         H, W = getattr(self.cfg, "mesh_render_size", (512, 512))
         turntable = MeshTurntable(int(H), int(W), dataset=getattr(self.cfg, "mesh_render_dataset", "zju_mocap"),
                                   device=getattr(self.cfg, "mesh_render_device", "cuda:0"))
-        return turntable.save(turntable.render(mesh, colors=colors), directory)
+        normals = mesh.vertex_normals if isinstance(mesh, TriMesh) and not colors else None
+        if normals is not None:
+            normals = torch.from_numpy(np.ascontiguousarray(normals, dtype=np.float32)).to(turntable.device)
+        return turntable.save(turntable.render(mesh, normals=normals, colors=colors), directory)

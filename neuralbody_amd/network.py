@@ -634,6 +634,104 @@ class Network(nn.Module):
                                                      precision=precision) for b in range(B)], 0)
         return self._decode(wpts, None, feature_volume, sp_input, True, precision).view(1, -1, 1)
 
+    # ------------------------------------------------------------------ d sigma / d p (no counterpart in the reference)
+    GRADIENT_CHUNK = 32768  # points per pass of calculate_density_gradient: their tap is 210 MB, the largest thing it holds
+
+    def _active_rows(self, feature_volume):
+        """(index grids, compact active rows) of the four levels, what nb_trilinear_grad reads: the encoder's own where the
+        FeatureVolumes object carries them; otherwise the active set of ops.sparsify (sized by ONE read-back of the four counts, as
+        the fold of foreign volumes is) and the rows it names, kept per volume tensors."""
+        fv = feature_volume if isinstance(feature_volume, FeatureVolumes) else None
+        if fv is not None and fv.sparse is not None and fv.rows is not None:
+            return [sp[0] for sp in fv.sparse], list(fv.rows)
+
+        def rows_of(vols, sparse):
+            out = []
+            for v, (_, lin, n_rows, cap) in zip(vols, sparse):
+                cap = max(int(cap), 1)
+                live = torch.arange(cap, device=v.device) < n_rows  # (entries behind the count are not voxel numbers)
+                out.append(v.reshape(-1, v.shape[3]).index_select(0, torch.where(live, lin[:cap].long(), 0)))
+            return out
+
+        if fv is not None and fv.sparse is not None:  # dense volumes with the encoder's index structures (the training path's)
+            def build():
+                vols = [ops.volume_as_channels_last(v) for v in fv]
+                return [sp[0] for sp in fv.sparse], rows_of(vols, fv.sparse)
+
+            return fv._memo.get("active_rows", (), build)
+
+        def build_foreign():
+            vols = [v if v.dim() == 4 else ops.volume_as_channels_last(v) for v in feature_volume]
+            sparse = [ops.sparsify(v) for v in vols]
+            counts = torch.cat([sp[2] for sp in sparse]).tolist()
+            sparse = [(g, lin, n, max(int(c), 1)) for (g, lin, n, _), c in zip(sparse, counts)]
+            return [sp[0] for sp in sparse], rows_of(vols, sparse)
+
+        return self._memo.get("foreign_rows", tkey(*feature_volume), build_foreign)
+
+    def _gradient_context(self, feature_volume, sp_input):
+        """What every chunk of calculate_density_gradient shares: the fp32 scene, the active rows, the packed weights, the latent
+        bias and the four weight matrices of the density branch."""
+        from .training import _w2
+
+        scene = self.make_scene(feature_volume, sp_input, "f32")
+        grids, rows = self._active_rows(feature_volume)
+        lb = self.latent_bias(sp_input["latent_index"], sp_input.get("_frame_token"))
+        return scene, grids, rows, lb, self.packed_weights("f32"), [_w2(m) for m in (self.fc_0, self.fc_1, self.fc_2, self.alpha_fc)]
+
+    def _gradient_chunk(self, ctx, pc, view=None, one=None, grad=None):
+        """One chunk: pc [k,3] contiguous -> (raw [k,4], tap [k,1600], d_feat [k,352], grad [k,3]); the caller drops the tap before it
+        decodes the next chunk.  view [k,3], one [k,1]: the constant view direction and the column of ones, made here when not given."""
+        scene, grids, rows, lb, packed, (W0, W1, W2, Wa) = ctx
+        k = pc.shape[0]
+        if view is None:
+            view = torch.zeros((k, 3), dtype=torch.float32, device=pc.device)
+            view[:, 2] = 1.0
+        if one is None:
+            one = torch.ones((k, 1), dtype=torch.float32, device=pc.device)
+        raw, tap = ops.decode_points(scene, packed, lb, pc, view, debug=True, precision="f32")
+        h1, h2, h3 = (tap[:, ops.TAP[name][0]:ops.TAP[name][1]] for name in ("h1", "h2", "h3"))
+        dh = ops.sgemm(one, Wa, relu_mask=h3)   # d sigma / d h3 (pre-activation): alpha_fc's weight where h3 > 0
+        dh = ops.sgemm(dh, W2, relu_mask=h2)
+        dh = ops.sgemm(dh, W1, relu_mask=h1)
+        d_feat = ops.sgemm(dh, W0)
+        return raw, tap, d_feat, ops.trilinear_grad(scene, grids, rows, pc, d_feat, out=grad)
+
+    def calculate_density_gradient(self, wpts, feature_volume, sp_input, chunk=GRADIENT_CHUNK):
+        """-> (sigma [B,n,1], grad [B,n,3]): the raw alpha_fc output `calculate_density` returns and its gradient d sigma / d p in
+        world axes.  Always the exact fp32 arithmetic, whatever `precision` the Network marches with.  Per chunk of points:
+        nb_decode_points with the activation tap (F | h1 | h2 | h3; the view direction is a constant and the colour half of the
+        decode is wasted), alpha_fc's weight under the mask h3 > 0, three nb_gemm_fused products down fc_2, fc_1, fc_0 with the
+        ReLU mask of the layer below in their epilogue (training.decoder_backward without the weight gradients) to d_feat
+        [n,352], and nb_trilinear_grad from there to the point (`_gradient_chunk`).  One chunk's tap, 210 MB at the default, is the
+        largest thing held: it is dropped before the next chunk is decoded."""
+        B = wpts.shape[0]
+        if B != 1:  # frame by frame, like calculate_density
+            outs = [self.calculate_density_gradient(wpts[b:b + 1], frame_volumes(feature_volume, b),
+                                                    frame_sp_input(dict(sp_input, batch_size=B), b), chunk=chunk)
+                    for b in range(B)]
+            return torch.cat([o[0] for o in outs], 0), torch.cat([o[1] for o in outs], 0)
+        chunk = int(chunk)
+        if chunk < 1:
+            raise ValueError("chunk must be >= 1, got %d" % chunk)
+        p = wpts.reshape(-1, 3).float().contiguous()
+        n = p.shape[0]
+        sigma = torch.empty((n, 1), dtype=torch.float32, device=p.device)
+        grad = torch.empty((n, 3), dtype=torch.float32, device=p.device)
+        if n == 0:
+            return sigma.view(1, 0, 1), grad.view(1, 0, 3)
+        ctx = self._gradient_context(feature_volume, sp_input)
+        view = torch.zeros((min(n, chunk), 3), dtype=torch.float32, device=p.device)
+        view[:, 2] = 1.0
+        one = torch.ones((min(n, chunk), 1), dtype=torch.float32, device=p.device)
+        for b in range(0, n, chunk):
+            pc = p[b:b + chunk]
+            k = pc.shape[0]
+            raw, tap, d_feat, _ = self._gradient_chunk(ctx, pc, view[:k], one[:k], grad[b:b + k])
+            sigma[b:b + k] = raw[:, 3:4]
+            del raw, tap, d_feat
+        return sigma.view(1, -1, 1), grad.view(1, -1, 3)
+
     LAST_DENSITY_FIX_RAYS = 4096  # rays per frame whose last density the unfused path re-decodes at fp32 (the nearest to zero)
 
     def fix_last_densities(self, raw, wpts, feature_volume, sp_input):
@@ -673,6 +771,10 @@ class Network(nn.Module):
         return self.calculate_density_color(light_pts[..., :3], viewdir[..., :3], feature_volume, sp_input)
 
     # ------------------------------------------------------------------ fused march
+    def t_vals(self, n_samples, device):
+        """torch.linspace(0, 1, N_samples) on the device (if_clight_renderer.py:13): a constant of (S, device), not of the frame."""
+        return self._memo.get("t_vals", (int(n_samples), str(device)), lambda: torch.linspace(0.0, 1.0, steps=int(n_samples)).to(device))
+
     def render_rays(self, ray_o, ray_d, near, far, feature_volume, sp_input, n_samples, t_rand=None,
                     white_bkgd=False, want_raw=False, ray_order=None, cull=None, order_covers_all=False):
         """All rays of the (single) batch element through nb_march.  ray_o/ray_d [n,3], near/far [n]."""
@@ -682,8 +784,7 @@ class Network(nn.Module):
             prec = self.march_precision()
             scene = self.make_scene(feature_volume, sp_input, prec)
         lb = self.latent_bias(sp_input["latent_index"], sp_input.get("_frame_token"))
-        t_vals = self._memo.get("t_vals", (int(n_samples), str(ray_o.device)),  # a constant of (S, device), not of the frame
-                                lambda: torch.linspace(0.0, 1.0, steps=int(n_samples)).to(ray_o.device))  # if_clight_renderer.py:13
+        t_vals = self.t_vals(n_samples, ray_o.device)
         ret = ops.march(scene, self.packed_weights(prec), lb, ray_o, ray_d, near, far, t_vals, t_rand,
                         white_bkgd=white_bkgd, want_raw=want_raw, precision=prec, ray_order=ray_order,
                         cull=cull, order_covers_all=order_covers_all, fixup=self.last_sample_fixup)

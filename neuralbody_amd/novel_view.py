@@ -224,8 +224,13 @@ class NovelViewRenderer:
             out = self.renderer.render(batch, t_rand=t_rand, feature_volume=self._frame_volumes(batch), **extra)
         img, depth = ops.image_assemble(batch["mask_at_box"][0], out["rgb_map"][0].contiguous(), out["depth_map"][0].contiguous(),
                                         white_bkgd=self.renderer.cfg.white_bkgd, bgr=bgr, scale=scale)
-        return {"img": img.view(self.H, self.W, 3), "depth": depth.view(self.H, self.W),
-                "mask_at_box": batch["mask_at_box"][0].view(self.H, self.W), "n_rays": n}
+        ret = {"img": img.view(self.H, self.W, 3), "depth": depth.view(self.H, self.W),
+               "mask_at_box": batch["mask_at_box"][0].view(self.H, self.W), "n_rays": n}
+        if "normal_map" in out:  # cfg.render_normals: the normal picture, 0.5 n + 0.5 over a black background (world axes as r, g, b)
+            normal_img, _ = ops.image_assemble(batch["mask_at_box"][0], (0.5 * out["normal_map"][0] + 0.5).contiguous(), bgr=bgr,
+                                               scale=scale)
+            ret["normal_img"] = normal_img.view(self.H, self.W, 3)
+        return ret
 
 
 def view_assignment(n_views, rank, world_size):

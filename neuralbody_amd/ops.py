@@ -875,6 +875,94 @@ def trilinear_bwd(scene, grids, drows, wpts, d_feat, run_length=1):
     return drows
 
 
+def trilinear_grad(scene, grids, rows, wpts, d_feat, out=None):
+    """nb_trilinear_grad: d_feat [n,352] -> grad [n,3] = d/dp sum_c d_feat[p,c] F_c(p) in world axes; rows[l]: the ACTIVE rows of
+    level l, compact [>= every id grids[l] holds, C_l] (the scene's dense volumes are not read)."""
+    sc, _keep = scene
+    _req(wpts, torch.float32, (None, 3), "wpts")
+    n = wpts.shape[0]
+    _req(d_feat, torch.float32, (n, 352), "d_feat")
+    dev = wpts.device
+    if out is None:
+        out = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    _req(out, torch.float32, (n, 3), "grad")
+    g4 = (C.c_void_p * 4)()
+    r4 = (C.c_void_p * 4)()
+    for l in range(4):
+        _req(grids[l], torch.int32, tuple(int(v) for v in sc.vol_dhw[l]), "grid[%d]" % l)
+        _req(rows[l], torch.float32, (None, LEVEL_CHANNELS[l]), "rows[%d]" % l)
+        g4[l] = grids[l].data_ptr()
+        r4[l] = rows[l].data_ptr()
+    for t, name in [(d_feat, "d_feat"), (out, "grad")] + [(x, "grids / rows") for x in list(grids) + list(rows)]:
+        if t.device != dev:
+            raise ValueError("trilinear_grad: %s lives on %s, wpts on %s" % (name, t.device, dev))
+    with torch.cuda.device(dev):
+        check(_lib.lib().nb_trilinear_grad(C.byref(sc), g4, r4, ptr(wpts), ptr(d_feat), n, ptr(out), _stream()), "nb_trilinear_grad")
+    return out
+
+
+def _march_rays(ray_o, ray_d, near, far, t_vals, t_rand, weights):
+    _req(ray_o, torch.float32, (None, 3), "ray_o")
+    n = ray_o.shape[0]
+    _req(ray_d, torch.float32, (n, 3), "ray_d")
+    _req(near, torch.float32, (n,), "near")
+    _req(far, torch.float32, (n,), "far")
+    _req(t_vals, torch.float32, (None,), "t_vals")
+    S = t_vals.shape[0]
+    if t_rand is not None:
+        _req(t_rand, torch.float32, (n, S), "t_rand")
+    _req(weights, torch.float32, (n, S), "weights")
+    if n * S >= 2 ** 31 - 256:
+        raise ValueError("%d rays x %d samples: the sample list holds fewer than 2^31 - 256" % (n, S))
+    return n, S
+
+
+def normal_select(ray_o, ray_d, near, far, t_vals, t_rand, weights, w_min, idx=None, wpts=None, scratch=None, n_out=None):
+    """nb_normal_select: the samples of a marched view with weights >= w_min, in (ray, sample) order, into idx [cap] int32
+    (= ray * S + s) and wpts [cap,3] fp32 (their positions by the march's own steps); both None: count only -> n_out, a [2] int32
+    device tensor {min(total, cap), total}; nothing is read back."""
+    n, S = _march_rays(ray_o, ray_d, near, far, t_vals, t_rand, weights)
+    dev = ray_o.device
+    if (wpts is None) != (idx is None):
+        raise ValueError("wpts and idx come together")
+    cap = 0
+    if wpts is not None:
+        _req(wpts, torch.float32, (None, 3), "wpts")
+        cap = min(int(wpts.shape[0]), 2 ** 31 - 1)
+        _req(idx, torch.int32, (int(wpts.shape[0]),), "idx")
+    if n_out is None:
+        n_out = torch.zeros(2, dtype=torch.int32, device=dev)  # (a view without samples launches nothing: the count is 0)
+    _req(n_out, torch.int32, (2,), "n_out")
+    if scratch is None:
+        scratch = scan_scratch(max(n * S, 1), dev)
+    with torch.cuda.device(dev):
+        check(_lib.lib().nb_normal_select(ptr(ray_o), ptr(ray_d), ptr(near), ptr(far), n, S, ptr(t_vals), ptr(t_rand), ptr(weights),
+                                          float(w_min), cap, ptr(idx), ptr(wpts), ptr(n_out), ptr(scratch), _stream()),
+              "nb_normal_select")
+    return n_out
+
+
+def normal_composite(idx, grad, weights, normal_map=None, normal_acc=None):
+    """nb_normal_composite: idx [m] int32 (normal_select's, ascending), grad [m,3] = d sigma / dp of those samples, weights [n,S]
+    -> (normal_map [n,3]: unit or zero, normal_acc [n]: the selected samples' weight); every ray is written."""
+    _req(weights, torch.float32, (None, None), "weights")
+    n, S = weights.shape
+    _req(idx, torch.int32, (None,), "idx")
+    m = idx.shape[0]
+    _req(grad, torch.float32, (m, 3), "grad")
+    dev = weights.device
+    if normal_map is None:
+        normal_map = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    if normal_acc is None:
+        normal_acc = torch.empty((n,), dtype=torch.float32, device=dev)
+    _req(normal_map, torch.float32, (n, 3), "normal_map")
+    _req(normal_acc, torch.float32, (n,), "normal_acc")
+    with torch.cuda.device(dev):
+        check(_lib.lib().nb_normal_composite(ptr(idx), ptr(grad), m, ptr(weights), n, S, ptr(normal_map), ptr(normal_acc), _stream()),
+              "nb_normal_composite")
+    return normal_map, normal_acc
+
+
 class ZeroArena:
     """One zero fill for everything a pass accumulates into (atomics, column sums, scatter targets): `take(shape, dtype)` hands
     out views of a single torch.zeros buffer sized by a planning pass over the same requests (`ZeroArena.plan()` counts)."""

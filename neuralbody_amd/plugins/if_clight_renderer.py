@@ -24,6 +24,10 @@ class _LiveCfg:
     W = property(lambda self: int(cfg.W * cfg.ratio))
     mesh_th = property(lambda self: float(cfg.mesh_th))
     mesh_backend = property(lambda self: str(getattr(cfg, "mesh_backend", "auto")))  # not a reference key: "auto" unless set
+    # field normals (not reference keys, absent = off): render() adds normal_map / normal_acc; the mesh takes its normals from the field
+    render_normals = property(lambda self: bool(getattr(cfg, "render_normals", False)))
+    normal_weight_min = property(lambda self: float(getattr(cfg, "normal_weight_min", 2.0 ** -8)))
+    mesh_normals = property(lambda self: str(getattr(cfg, "mesh_normals", "faces")))
 
 
 class Renderer(_Renderer):

@@ -21,7 +21,8 @@ class RenderConfig:
     """The cfg keys the hot path reads."""
 
     def __init__(self, N_samples=64, perturb=0.0, raw_noise_std=0.0, white_bkgd=False, H=None, W=None, mesh_th=50.0,
-                 mesh_backend="auto", mesh_components="all", mesh_color=False):
+                 mesh_backend="auto", mesh_components="all", mesh_color=False, render_normals=False, normal_weight_min=2.0 ** -8,
+                 mesh_normals="faces"):
         # H, W (optional): image size of the view the rays come from (cfg.H * cfg.ratio in the reference); when
         # batch['mask_at_box'] covers H*W pixels, rays are marched in 8x8 pixel tiles
         self.H, self.W = H, W
@@ -37,6 +38,12 @@ class RenderConfig:
         # or a fraction in (0, 1] of the largest one's faces) and whether every vertex gets a colour from the colour head
         self.mesh_components = mesh_components
         self.mesh_color = bool(mesh_color)
+        # field normals (not reference keys, off unless set): render() adds normal_map / normal_acc from the gradient of the density at
+        # the samples whose weight is at least normal_weight_min; RendererMesh takes the vertex normals from the field ("field")
+        # instead of the triangles ("faces")
+        self.render_normals = bool(render_normals)
+        self.normal_weight_min = float(normal_weight_min)
+        self.mesh_normals = str(mesh_normals)
 
 
 class ColoredMesh(collections.namedtuple("ColoredMesh", "vertices triangles rgb_f rgb_u8 wpts viewdir normals")):
@@ -163,19 +170,29 @@ class Renderer:
         return raw
 
     # -- if_clight_renderer.py:94-122
-    def render(self, batch, t_rand=None, want_raw=False, ray_range=None, feature_volume=None, raw_noise=None, prefetched=None):
+    def render(self, batch, t_rand=None, want_raw=False, ray_range=None, feature_volume=None, raw_noise=None, prefetched=None,
+               normals=None):
         """ray_range = (begin, end) renders a contiguous slice of the rays (multi-GPU sharding).
+        normals (None: cfg.render_normals, absent = off): adds normal_map [B,n,3], the surface normal of the density field in world
+        axes (unit, or zero where nothing was selected), and normal_acc [B,n], the weight of the samples it blends (`_field_normals`;
+        inference only).  Without it the dict and the launches are what they were.
         prefetched: ticket of `prefetch(batch)` — this frame's encoder pass, enqueued earlier on a second stream.
         feature_volume: volumes of a previous `net.encode_sparse_voxels` of the SAME frame (same coord, out_sh, weights):
         the encoder is then skipped — novel-view loops render many views of one frame (NovelViewRenderer.reuse_volumes)."""
         ray_o, ray_d, near, far = batch["ray_o"], batch["ray_d"], batch["near"], batch["far"]
         n_batch, n_pixel = ray_o.shape[:2]
+        asked_value, asked = normals, bool(normals)  # (by the caller; the cfg key alone leaves a training step as it is)
+        if normals is None:
+            normals = bool(getattr(self.cfg, "render_normals", False))
         if n_batch != 1:
-            return self._render_frames(batch, n_batch, t_rand, want_raw, ray_range, feature_volume, raw_noise)
+            # (the caller's own value goes down, not the resolved one: the cfg key alone never stops a training step, B > 1 included)
+            return self._render_frames(batch, n_batch, t_rand, want_raw, ray_range, feature_volume, raw_noise, asked_value)
         if torch.is_grad_enabled() and ray_range is None and any(p.requires_grad for p in self.net.parameters()):
             # training step (lib/train/trainers/if_nerf_clight.py:18-36): differentiable HIP path
             from . import training
 
+            if asked:
+                raise NotImplementedError("field normals are inference-only (wrap the call in torch.no_grad(), as run.py:66,98 does)")
             if feature_volume is not None or want_raw or self.make_cull(batch) is not None:
                 raise NotImplementedError("the differentiable path renders all samples of the batch from its own encoder pass: "
                                           "feature_volume / want_raw / sample culling are inference-only (wrap the call in "
@@ -222,9 +239,35 @@ class Renderer:
             rgb, disp, acc, weights, depth = ops.composite(raw, z_vals[0].contiguous(), ray_d[0, b:e].contiguous(), self.cfg.white_bkgd)
             ret = {"rgb_map": rgb, "disp_map": disp, "acc_map": acc, "weights": weights, "depth_map": depth,
                    **({"raw": raw} if want_raw else {})}
+        if normals:
+            ret["normal_map"], ret["normal_acc"] = self._field_normals(
+                ret["weights"], ray_o[0, b:e].contiguous(), ray_d[0, b:e].contiguous(), near[0, b:e].contiguous(),
+                far[0, b:e].contiguous(), tr, feature_volume, sp_input)
         return {k: v[None] for k, v in ret.items()}
 
-    def _render_frames(self, batch, n_batch, t_rand, want_raw, ray_range, feature_volume, raw_noise):
+    def _field_normals(self, weights, ray_o, ray_d, near, far, t_rand, feature_volume, sp_input):
+        """(normal_map [n,3], normal_acc [n]) behind a march: nb_normal_select lists the samples with weights >= cfg.normal_weight_min
+        (default 2^-8; culled samples have weight 0 and are never listed) with the positions the march decoded — its count pass runs
+        first and the 8-byte count is the one read-back, the capacity rule of the mesh lattice —, Network.calculate_density_gradient
+        gives d sigma / dp there (exact fp32 whatever arithmetic marched), nb_normal_composite blends -grad / |grad| per ray."""
+        n, S = weights.shape
+        dev = weights.device
+        weights = weights.contiguous()
+        t_vals = self.net.t_vals(S, dev)
+        w_min = float(getattr(self.cfg, "normal_weight_min", 2.0 ** -8))
+        total = 0
+        if n * S:
+            scratch = ops.scan_scratch(n * S, dev)
+            total = int(ops.normal_select(ray_o, ray_d, near, far, t_vals, t_rand, weights, w_min, scratch=scratch)[1].item())
+        idx = torch.empty(total, dtype=torch.int32, device=dev)
+        wpts = torch.empty((total, 3), dtype=torch.float32, device=dev)
+        grad = torch.empty((total, 3), dtype=torch.float32, device=dev)
+        if total:
+            ops.normal_select(ray_o, ray_d, near, far, t_vals, t_rand, weights, w_min, idx, wpts, scratch=scratch)
+            grad = self.net.calculate_density_gradient(wpts[None], feature_volume, sp_input)[1][0]
+        return ops.normal_composite(idx, grad, weights)
+
+    def _render_frames(self, batch, n_batch, t_rand, want_raw, ray_range, feature_volume, raw_noise, normals=None):
         """A batch of B > 1 frames (lib/config/config.py:81 defaults train.batch_size to 4; every shipped YAML sets 1): B renders of
         one frame each — differentiable or not — stacked along the batch dimension.  The reference itself cannot run this case (its
         Network pairs ONE set of 6890 vertex codes with the B * 6890 coordinates of the batch, latent_xyzc.py:35-36, which spconv
@@ -239,7 +282,7 @@ class Renderer:
             sub["out_sh"] = out_sh
             fv = None if feature_volume is None else frame_volumes(feature_volume, b)
             outs.append(self.render(sub, t_rand=None if t_rand is None else t_rand[b:b + 1], want_raw=want_raw, ray_range=ray_range,
-                                    feature_volume=fv, raw_noise=None if raw_noise is None else raw_noise[b:b + 1]))
+                                    feature_volume=fv, raw_noise=None if raw_noise is None else raw_noise[b:b + 1], normals=normals))
         return {k: torch.cat([o[k] for o in outs], 0) for k in outs[0]}
 
     # -- the encoder of the NEXT frame under the march of this one (no counterpart in the reference, whose render() is one
@@ -528,7 +571,7 @@ class RendererMesh(Renderer):
         step, origin = self._world_frame(batch, vertices)
         return (vertices - float(pad)) * step + origin
 
-    def extract_mesh(self, batch, world=False, cube=None, components="all", colors=False, volumes=None):
+    def extract_mesh(self, batch, world=False, cube=None, components="all", colors=False, volumes=None, normals="faces"):
         """-> DEVICE (vertices [V,3] float32, triangles [T,3] int32) of the iso-surface cube == cfg.mesh_th (ops.marching_cubes;
         the cube stays on the device).  Vertices in index units of the padded cube like PyMCubes', or in world units.
         components: "all" — every closed surface the threshold leaves, what marching cubes returns (no further launch);
@@ -539,7 +582,13 @@ class RendererMesh(Renderer):
         [V,3] and rgb_u8 uint8 [V,3], the colour head's answer at every vertex of the (cleaned) mesh, seen along -normal from
         outside, the normals being those of the WORLD vertices; and wpts, viewdir, normals, what the head was asked.  ONE
         calculate_density_color call on the feature volumes the cube was decoded from: `volumes` is what `_density_cube` returned
-        beside `cube` (with neither given, both are made here; the frame is encoded once)."""
+        beside `cube` (with neither given, both are made here; the frame is encoded once).
+        normals (with colors): "faces" — the area-weighted face normals of the mesh (ops.mesh_vertex_normals); "field" — the normal
+        of the density field itself, -grad sigma / |grad sigma| at the world vertices (Network.calculate_density_gradient on the same
+        feature volumes, normalised by nb_normal_composite with every vertex a ray of one sample); a vertex whose gradient is zero or
+        not finite keeps its face normal."""
+        if normals not in ("faces", "field"):
+            raise ValueError("normals must be 'faces' or 'field', got %r" % (normals,))
         if cube is None:
             cube, volumes = self._density_cube(batch)
         vertices, triangles = ops.marching_cubes(cube.contiguous(), self.cfg.mesh_th)
@@ -553,7 +602,16 @@ class RendererMesh(Renderer):
         if volumes is None:  # a cube from elsewhere: its frame is encoded here
             volumes = self._volumes(batch)
         wverts = self._to_world(vertices, batch)
-        normals = ops.mesh_vertex_normals(wverts, triangles)
+        face_normals = ops.mesh_vertex_normals(wverts, triangles)
+        if normals == "field" and wverts.shape[0]:
+            feature_volume, sp_input = volumes()
+            grad = self.net.calculate_density_gradient(wverts[None].contiguous(), feature_volume, sp_input)[1][0]
+            V = wverts.shape[0]
+            unit, _ = ops.normal_composite(torch.arange(V, dtype=torch.int32, device=wverts.device), grad,
+                                           torch.ones((V, 1), dtype=torch.float32, device=wverts.device))
+            normals = torch.where((unit != 0).any(1, keepdim=True), unit, face_normals).contiguous()
+        else:
+            normals = face_normals
         step, origin = self._world_frame(batch, vertices)
 
         def decode(wpts, viewdir):
@@ -569,22 +627,27 @@ class RendererMesh(Renderer):
         return lambda: held
 
     def render(self, batch):
-        """if_mesh_renderer.py:26-54 -> {"cube", "mesh"}.  cfg.mesh_components / cfg.mesh_color (YAML-only keys like mesh_render,
-        absent = off) ask for `extract_mesh`'s clean-up and vertex colours: with either set the mesh is extracted on the device
+        """if_mesh_renderer.py:26-54 -> {"cube", "mesh"}.  cfg.mesh_components / cfg.mesh_color / cfg.mesh_normals: field (YAML-only
+        keys like mesh_render, absent = off) ask for `extract_mesh`'s clean-up, vertex colours and field normals (TriMesh.vertex_normals,
+        written as nx ny nz and handed to the turntable): with any of them set the mesh is extracted on the device
         whatever cfg.mesh_backend says (PyMCubes has neither), and `mesh` is a mesh.TriMesh, the class that carries
         vertex_colors."""
         backend = getattr(self.cfg, "mesh_backend", "auto")
         if backend not in ("auto", "device"):
             raise ValueError("mesh_backend must be 'auto' or 'device', got %r" % (backend,))
         components, colors = getattr(self.cfg, "mesh_components", "all"), bool(getattr(self.cfg, "mesh_color", False))
-        if ops.mesh_components_fraction(components) is not None or colors:
+        normals = str(getattr(self.cfg, "mesh_normals", "faces"))
+        if ops.mesh_components_fraction(components) is not None or colors or normals == "field":
             from .mesh import TriMesh
 
             cube_dev, volumes = self._density_cube(batch)
-            mesh = self.extract_mesh(batch, cube=cube_dev, components=components, colors=colors, volumes=volumes)
+            # (the field normals come with the colour query: the colour head is asked along them; the colours are kept only if asked for)
+            mesh = self.extract_mesh(batch, cube=cube_dev, components=components, colors=colors or normals == "field", volumes=volumes,
+                                     normals=normals)
             cube = cube_dev.double().cpu().numpy()
             return {"cube": cube, "mesh": TriMesh(mesh[0].double().cpu().numpy(), mesh[1].cpu().numpy(),
-                                                  vertex_colors=mesh.rgb_u8.cpu().numpy() if colors else None)}
+                                                  vertex_colors=mesh.rgb_u8.cpu().numpy() if colors else None,
+                                                  vertex_normals=mesh.normals.cpu().numpy() if normals == "field" else None)}
         mcubes = None
         if backend == "auto":
             try:
