@@ -20,22 +20,28 @@ struct RayCam {
     float bmin[3], bmax[3];
 };
 
+// The arithmetic below is written with plain operators under a contraction pragma of its own (as in nb_march_common.h): the `_rn`
+// intrinsics are the plain operators to hipcc, which contracts them into FMAs across the inlined calls, so the norm used to be
+// fma(dx, dx, dy * dy) + dz * dz and near / far of an oblique view differed from the reference's by up to 2 ulp
+// (tests/test_gpu_raygen.py).  Under the pragma each operation is ONE IEEE operation, as in numpy; `/` and sqrtf are the correctly
+// rounded ones of this toolchain.
+
 // fp64 direction of the ray through pixel (px, py): pixel_world - rays_o before the cast
 __device__ __forceinline__ void pixel_ray_f64(const RayCam &c, int px, int py, double (&d)[3]) {
+#pragma clang fp contract(off)
     // xy1 is float32 in the reference (np.arange(..., dtype=float32)), promoted to float64 by np.dot
     const double x = (double)(float)px, y = (double)(float)py;
     double pc[3], pw[3];
 #pragma unroll
     for (int a = 0; a < 3; ++a)  // xy1 @ inv(K).T
-        pc[a] = __dadd_rn(__dadd_rn(__dmul_rn(x, c.Kinv[a * 3 + 0]), __dmul_rn(y, c.Kinv[a * 3 + 1])), c.Kinv[a * 3 + 2]);
+        pc[a] = (x * c.Kinv[a * 3 + 0] + y * c.Kinv[a * 3 + 1]) + c.Kinv[a * 3 + 2];
 #pragma unroll
-    for (int a = 0; a < 3; ++a) pc[a] = __dsub_rn(pc[a], c.T[a]);
+    for (int a = 0; a < 3; ++a) pc[a] = pc[a] - c.T[a];
 #pragma unroll
     for (int a = 0; a < 3; ++a)  // (pixel_camera - T) @ R
-        pw[a] = __dadd_rn(__dadd_rn(__dmul_rn(pc[0], c.R[0 * 3 + a]), __dmul_rn(pc[1], c.R[1 * 3 + a])),
-                          __dmul_rn(pc[2], c.R[2 * 3 + a]));
+        pw[a] = (pc[0] * c.R[0 * 3 + a] + pc[1] * c.R[1 * 3 + a]) + pc[2] * c.R[2 * 3 + a];
 #pragma unroll
-    for (int a = 0; a < 3; ++a) d[a] = __dsub_rn(pw[a], c.o[a]);
+    for (int a = 0; a < 3; ++a) d[a] = pw[a] - c.o[a];
 }
 
 __device__ __forceinline__ void pixel_ray(const RayCam &c, int px, int py, float (&o)[3], float (&d)[3]) {
@@ -51,41 +57,42 @@ __device__ __forceinline__ void pixel_ray(const RayCam &c, int px, int py, float
 // get_near_far on the float32 rays of a full image (render_utils.py:126-127 casts before it intersects)
 __device__ __forceinline__ bool near_far(const RayCam &c, const float (&o)[3], const float (&d)[3], float *near,
                                          float *far) {
-    const float n = sqrtf(__fadd_rn(__fadd_rn(__fmul_rn(d[0], d[0]), __fmul_rn(d[1], d[1])), __fmul_rn(d[2], d[2])));
+#pragma clang fp contract(off)
+    const float n = sqrtf((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]);
     float tn = -INFINITY, tf = INFINITY;
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
-        float v = __fdiv_rn(d[a], n);
+        float v = d[a] / n;
         if (v < 1e-5f && v > -1e-10f) v = 1e-5f;   // if_nerf_data_utils.py:58
         if (v > -1e-5f && v < 1e-10f) v = -1e-5f;  // :59 (order matters)
-        const float t0 = __fdiv_rn(__fsub_rn(c.bmin[a], o[a]), v);
-        const float t1 = __fdiv_rn(__fsub_rn(c.bmax[a], o[a]), v);
+        const float t0 = (c.bmin[a] - o[a]) / v;
+        const float t1 = (c.bmax[a] - o[a]) / v;
         tn = fmaxf(tn, fminf(t0, t1));
         tf = fminf(tf, fmaxf(t0, t1));
     }
-    *near = __fdiv_rn(tn, n);
-    *far = __fdiv_rn(tf, n);
+    *near = tn / n;
+    *far = tf / n;
     return tn < tf;
 }
 
 // get_near_far on the float64 rays of a training batch (if_nerf_data_utils.py:116-120 hands it get_rays' own arrays; the
 // float32 bounds are promoted); near and far leave as float64 and are rounded once where they are stored (:134-135)
 __device__ __forceinline__ bool near_far(const RayCam &c, const double (&d)[3], double *near, double *far) {
-#pragma clang fp contract(off)  // every operation below is one IEEE float64 operation, like numpy's
-    const double n = __dsqrt_rn(__dadd_rn(__dadd_rn(__dmul_rn(d[0], d[0]), __dmul_rn(d[1], d[1])), __dmul_rn(d[2], d[2])));
+#pragma clang fp contract(off)
+    const double n = __dsqrt_rn((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]);
     double tn = -INFINITY, tf = INFINITY;
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
-        double v = __ddiv_rn(d[a], n);
+        double v = d[a] / n;
         if (v < 1e-5 && v > -1e-10) v = 1e-5;   // if_nerf_data_utils.py:58
         if (v > -1e-5 && v < 1e-10) v = -1e-5;  // :59 (order matters)
-        const double t0 = __ddiv_rn(__dsub_rn((double)c.bmin[a], c.o[a]), v);
-        const double t1 = __ddiv_rn(__dsub_rn((double)c.bmax[a], c.o[a]), v);
+        const double t0 = ((double)c.bmin[a] - c.o[a]) / v;
+        const double t1 = ((double)c.bmax[a] - c.o[a]) / v;
         tn = fmax(tn, fmin(t0, t1));
         tf = fmin(tf, fmax(t0, t1));
     }
-    *near = __ddiv_rn(tn, n);
-    *far = __ddiv_rn(tf, n);
+    *near = tn / n;
+    *far = tf / n;
     return tn < tf;
 }
 

@@ -186,6 +186,25 @@ def run_raygen():
     print("raygen ->", path, "%.0f KB" % (os.path.getsize(path) / 1024))
 
 
+def run_raygen_edges():
+    """image_rays (render_utils.py:120-137, i.e. get_rays and get_near_far) on the edge cases of tests/ray_cases.py but the
+    sizes_* ones, which differ from W1 / H1 in the launch shape alone."""
+    ns = rh.load()
+    from tests import ray_cases as rc
+
+    g = {}
+    for name, H, W, K, R, T, bounds in rc.CASES:
+        if name.startswith("sizes_"):
+            continue
+        ns.cfg.H, ns.cfg.W, ns.cfg.ratio = H, W, 1.0
+        _ro, rd, near, far, _c, _s, mask = ns.image_rays(np.concatenate([R, T], 1), K, bounds)
+        assert mask.shape == (H * W,) and rd.dtype == near.dtype == far.dtype == np.float32
+        g.update({name + "_mask": mask, name + "_ray_d": rd, name + "_near": near, name + "_far": far})
+    path = os.path.join(OUT, "raygen_edges.npz")
+    np.savez_compressed(path, **g)
+    print("raygen_edges ->", path, "%.0f KB" % (os.path.getsize(path) / 1024))
+
+
 def run_masked(kind):
     """The reference's mask-culled renderers (lib/networks/renderer/if_clight_renderer_mmsk.py / _msk.py) on CPU."""
     import importlib
@@ -397,10 +416,12 @@ def run_trained():
 
 if __name__ == "__main__":
     torch.manual_seed(0)
-    names = sys.argv[1:] or list(scenes.SCENES) + ["raygen", "train", "mmsk", "msk", "mesh", "novel", "trained", "batch2"] + ["bench:" + t for t in scenes.BENCH]
+    names = sys.argv[1:] or list(scenes.SCENES) + ["raygen", "raygen_edges", "train", "mmsk", "msk", "mesh", "novel", "trained", "batch2"] + ["bench:" + t for t in scenes.BENCH]
     for n in names:
         if n == "raygen":
             run_raygen()
+        elif n == "raygen_edges":
+            run_raygen_edges()
         elif n == "train":
             run_train_step()
         elif n == "trained":

@@ -139,6 +139,26 @@ def test_oracle_raygen_matches_reference_golden(golden_dir):
         np.testing.assert_array_equal(ro[0], g[tag + "_ray_o"])
 
 
+def test_oracle_and_restatement_match_the_reference_on_the_ray_edge_cases(golden_dir):
+    """tests/golden/raygen_edges.npz (make_golden.py::run_raygen_edges, the reference's image_rays): the oracle and the float32
+    restatement of csrc/nb_ray.h give its masks, and the kept rays' directions, near and far bit for bit."""
+    from tests import ray_cases as rc
+
+    g = np.load(os.path.join(golden_dir, "raygen_edges.npz"))
+    names = [c[0] for c in rc.CASES if not c[0].startswith("sizes_")]
+    assert sorted(g.files) == sorted(n + s for n in names for s in ("_mask", "_ray_d", "_near", "_far"))
+    for name in names:
+        _, H, W, K, R, T, bounds = rc.BY_NAME[name]
+        mask = g[name + "_mask"]
+        _, rd, near, far, omask = orc.image_rays(H, W, K, R, T, bounds)
+        _, d, near32, far32, hit = rc.image_rays32(H, W, K, R, T, bounds)
+        assert mask.dtype == bool and np.array_equal(omask, mask) and np.array_equal(hit, mask), name
+        for k, a, b in (("ray_d", rd, d[hit]), ("near", near, near32[hit]), ("far", far, far32[hit])):
+            assert rc.ulp_diff(a, g[name + "_" + k]) == 0 and rc.ulp_diff(b, g[name + "_" + k]) == 0, (name, k)
+    assert not g["slab_p8_mask"].any() and g["inside_mask"].all() and g["behind_mask"].all() and (g["behind_far"] < 0).all()
+    assert int(g["tie_mask"].sum()) == 8 and not g["tie_mask"][list(rc.TIES["tie"])].any()
+
+
 def test_oracle_autograd_matches_reference_training_step(golden_dir):
     """The oracle under autograd against the gradients the UNMODIFIED reference produced for one training step
     (tests/golden/train_step.npz, made by make_golden.py: NetworkWrapper on CPU): loss, and per parameter the
