@@ -182,6 +182,9 @@ int nb_decode_points(const nb_scene *scene, const float *packed, const float *la
  * is decoded only if it projects inside every one of n_views silhouettes; culled samples get raw = 0
  * (if_clight_renderer_mmsk.py:54-59).  pre_affine != 0 (the _msk variant) first maps the point
  * world -> SMPL space of the rendered pose (scene R, Th) -> world of the snapshot frame (R0, Th0).
+ * Arithmetic, fp32: every row of a 3x3 product is the ascending FMA chain fma(p2, m2, fma(p1, m1, p0 * m0)) — what the
+ * reference's matrix products evaluate to on the CPU —, a translation is a separate add, the perspective division IEEE;
+ * the pixel is rint (half to even) clamped to the mask, a coordinate that is not finite or beyond 9e18 reads pixel 0.
  * ------------------------------------------------------------------------------- */
 #define NB_SLOT_DEAD (-2147483647 - 1) /* nb_march ray_order: empty slot */
 #define NB_MAX_CULL_VIEWS 64 /* the reference loops over batch['Ks'].size(1) training views (4 or 6 in the shipped configs) */
@@ -638,7 +641,7 @@ int nb_smpl_voxelize(const float *verts, int32_t n_verts, int32_t n_frames, cons
  *   verts dev [F,V,3] fp32 (nb_smpl_pose); faces dev [Nf,3] int32 vertex indices, either winding (a face with an index outside
  *   0..V-1 is skipped; neuralbody_amd/smpl_pose.py::SmplModel validates the list once on the host); cam dev [nv,21] fp32, the
  *   layout of nb_cull.cam (RT 3x4 | K 3x3).  out dev [F,nv,H,W] uint8, 1 = body; a dirty buffer is fine.
- *   Projection: p = R v + T, (u, w) = (K p).xy / (K p).z in fp32, nb_cull's operations in nb_cull's order.  u, w are snapped to 1/256
+ *   Projection: p = R v + T, (u, w) = (K p).xy / (K p).z in fp32, nb_cull's arithmetic (FMA chains, above; one device function serves both).  u, w are snapped to 1/256
  *   pixel (rintf(256 u), half to even) and held as integers.  Pixel (x, y) is the closed unit square centred on the integer
  *   point (x, y).  Coverage is conservative and exact: a pixel is set for a triangle iff its square meets the closed snapped
  *   triangle — the square overlaps the triangle's bounding box and, with the triangle oriented to positive area, every int64

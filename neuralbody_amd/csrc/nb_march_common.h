@@ -100,7 +100,12 @@ struct FoldDev {
     unsigned zero_off;  // byte offset of the all-zero row
 };
 
-// sample culling against training-view silhouettes (nb_cull): the reference's fp32 operation order
+// sample culling against training-view silhouettes (nb_cull).  The projection is the reference's fp32 arithmetic as its CPU
+// BLAS carries it out (torch.matmul in the renderers, np.dot in the mesh dataset): a row of a 3 x 3 product is the ascending FMA
+// chain fma(p2, m2, fma(p1, m1, p0 * m0)), the translation a separate add, the perspective division IEEE.  It is written with
+// explicit fmaf under a contraction pragma of its own, so that no compiler choice is left (the `_rn` intrinsics are plain operators
+// to hipcc, which contracted some of them and not others).  tests/golden/cull_edges.npz records the reference on points bisected
+// to pixel edges; tests/test_gpu_cull.py holds every kernel that culls to tests/cull_cases.py::chain on them, at 0 differing points.
 struct CullDev {
     int n_views, H, W, pre;
     const unsigned char *msk;  // [n_views, H, W]
@@ -116,53 +121,44 @@ __device__ __forceinline__ int cull_pixel(float f, int size) {
     return (int)fminf(fmaxf(r, 0.f), (float)(size - 1));
 }
 
+// a0 m0 + a1 m1 + a2 m2 as the ascending FMA chain
+__device__ __forceinline__ float cull_dot3(float a0, float a1, float a2, float m0, float m1, float m2) {
+#pragma clang fp contract(off)
+    return fmaf(a2, m2, fmaf(a1, m1, a0 * m0));
+}
+
+// One view's projection: t = RT . (p, 1), q = K . t; the pixel is q.xy / q.z under __fdiv_rn.  The ONE statement of it: cull_inside
+// below and nb_silhouette.hip (which needs the numbers and not the mask lookup) both call it.
+__device__ __forceinline__ void cull_project(cfloat_ptr RT, const float p[3], float t[3], float q[3]) {
+#pragma clang fp contract(off)
+    cfloat_ptr K = RT + 12;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) t[i] = cull_dot3(p[0], p[1], p[2], RT[i * 4], RT[i * 4 + 1], RT[i * 4 + 2]) + RT[i * 4 + 3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) q[i] = cull_dot3(t[0], t[1], t[2], K[i * 3], K[i * 3 + 1], K[i * 3 + 2]);
+}
+
 __device__ __forceinline__ bool cull_inside(const CullDev &c, const SceneDev &sc, float px, float py, float pz) {
+#pragma clang fp contract(off)
     float p[3] = {px, py, pz};
-    if (c.pre) {  // if_clight_renderer_msk.py:18-32
+    if (c.pre) {  // if_clight_renderer_msk.py:18-29: q = p - Th, can = q R, p = can R0^T + Th0
         const Pose ps = load_pose(sc.pose);
         cfloat_ptr sn = (cfloat_ptr)c.snap;
-        const float q[3] = {__fsub_rn(px, ps.Th[0]), __fsub_rn(py, ps.Th[1]), __fsub_rn(pz, ps.Th[2])};
+        const float q[3] = {px - ps.Th[0], py - ps.Th[1], pz - ps.Th[2]};
         float can[3];
 #pragma unroll
-        for (int j = 0; j < 3; ++j)
-            can[j] = __fadd_rn(__fadd_rn(__fmul_rn(q[0], ps.R[j]), __fmul_rn(q[1], ps.R[3 + j])), __fmul_rn(q[2], ps.R[6 + j]));
+        for (int j = 0; j < 3; ++j) can[j] = cull_dot3(q[0], q[1], q[2], ps.R[j], ps.R[3 + j], ps.R[6 + j]);
 #pragma unroll
-        for (int i = 0; i < 3; ++i)
-            p[i] = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(can[0], sn[i * 3]), __fmul_rn(can[1], sn[i * 3 + 1])),
-                                       __fmul_rn(can[2], sn[i * 3 + 2])), sn[9 + i]);
+        for (int i = 0; i < 3; ++i) p[i] = cull_dot3(can[0], can[1], can[2], sn[i * 3], sn[i * 3 + 1], sn[i * 3 + 2]) + sn[9 + i];
     }
     bool inside = true;
     for (int v = 0; v < c.n_views; ++v) {  // if_clight_renderer_mmsk.py:21-38 (loops over batch['Ks'].size(1) views)
-        cfloat_ptr RT = (cfloat_ptr)(c.cam + v * 21), K = RT + 12;
         float t[3], q[3];
-#pragma unroll
-        for (int i = 0; i < 3; ++i)
-            t[i] = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(p[0], RT[i * 4]), __fmul_rn(p[1], RT[i * 4 + 1])),
-                                       __fmul_rn(p[2], RT[i * 4 + 2])), RT[i * 4 + 3]);
-#pragma unroll
-        for (int i = 0; i < 3; ++i)
-            q[i] = __fadd_rn(__fadd_rn(__fmul_rn(t[0], K[i * 3]), __fmul_rn(t[1], K[i * 3 + 1])),
-                             __fmul_rn(t[2], K[i * 3 + 2]));
+        cull_project((cfloat_ptr)(c.cam + v * 21), p, t, q);
         const int x = cull_pixel(__fdiv_rn(q[0], q[2]), c.W), y = cull_pixel(__fdiv_rn(q[1], q[2]), c.H);
         inside = inside && c.msk[((size_t)v * c.H + y) * c.W + x] != 0;
     }
     return inside;
-}
-
-// One view's projection of cull_inside, operation for operation, for code that needs the numbers and not the mask lookup
-// (nb_silhouette.hip): t = RT . (p, 1), q = K . t; the pixel is q.xy / q.z under __fdiv_rn.  These eight lines DUPLICATE the loop
-// body of cull_inside, which is left as it is; a change to either must be made to both.  What holds them together is
-// tests/test_gpu_silhouette.py: every device mask equals silhouette_ref.snapped_mask, the same operations in numpy float32.
-__device__ __forceinline__ void cull_project(cfloat_ptr RT, const float p[3], float t[3], float q[3]) {
-    cfloat_ptr K = RT + 12;
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-        t[i] = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(p[0], RT[i * 4]), __fmul_rn(p[1], RT[i * 4 + 1])),
-                                   __fmul_rn(p[2], RT[i * 4 + 2])), RT[i * 4 + 3]);
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-        q[i] = __fadd_rn(__fadd_rn(__fmul_rn(t[0], K[i * 3]), __fmul_rn(t[1], K[i * 3 + 1])),
-                         __fmul_rn(t[2], K[i * 3 + 2]));
 }
 
 struct MarchArgs {

@@ -414,14 +414,70 @@ def run_trained():
           "%.0f KB" % (os.path.getsize(path) / 1024))
 
 
+def run_cull_edges():
+    """The reference's three sample culls on the pixel-edge points of tests/cull_cases.py against the checkerboard mask:
+    if_clight_renderer_mmsk.Renderer.prepare_inside_pts (every set but 'pre'), if_clight_renderer_msk.Renderer.prepare_inside_pts
+    ('pre', the set with R, Th, R0_snap, Th0_snap) and multi_view_mesh_dataset.Dataset.prepare_inside_pts, i.e. base_utils.project
+    (every set but 'pre').  All points of a set go through ONE call and its row count is recorded: torch multiplies matrices of 7 rows
+    or fewer with other arithmetic.  The _msk renderer's first product is batched per pixel ([n_pixel, n_sample, 3] x [3, 3]): the
+    points are laid out as rows of MSK_SAMPLES = 64 samples (the shipped N_samples; the last row padded by repeating the last point),
+    since that product too changes its arithmetic with the row count.  The mesh dataset is built without its file-reading constructor;
+    get_mask serves the checkerboard.  The fixture holds the points and the three answers: data only."""
+    import importlib
+
+    from tests import cull_cases as cc
+    from tests.golden import make_golden_mesh_lattice as ml
+
+    ml.seed_modules()  # cv2 / imageio / plyfile stand-ins the mesh dataset's module imports (none is called here)
+    ns = rh.load()
+    cfg = ns.cfg
+    cfg.H, cfg.W, cfg.ratio = cc.H, cc.W, 1.0
+    mmsk = importlib.import_module("lib.networks.renderer.if_clight_renderer_mmsk").Renderer(None)
+    msk = importlib.import_module("lib.networks.renderer.if_clight_renderer_msk").Renderer(None)
+    mvm = importlib.import_module("lib.datasets.light_stage.multi_view_mesh_dataset")
+    board = cc.checkerboard()
+    MSK_SAMPLES = 64
+    g = {"msk_samples": np.array(MSK_SAMPLES), "torch_version": np.array(torch.__version__), "numpy_version": np.array(np.__version__)}
+    for name in cc.SET_NAMES:
+        cam, p = cc.camera(name), cc.points(name)
+        n = len(p)
+        g[name + "/points"] = p
+        g[name + "/rows"] = np.array(n)
+        assert n > 7
+        with torch.no_grad(), np.errstate(all="ignore"):
+            if name == "pre":
+                pad = (-n) % MSK_SAMPLES
+                wpts = torch.from_numpy(np.concatenate([p, np.repeat(p[-1:], pad, 0)])).view(1, -1, MSK_SAMPLES, 3)
+                batch = {"Th": cam["Th"][None], "R": cam["R"][None], "R0_snap": cam["R0"][None], "Th0_snap": cam["Th0"][None],
+                         "RT": cam["RT"][None], "K": cam["K"][None], "msk": board[None]}
+                ins = msk.prepare_inside_pts(wpts, rh.torch_batch(batch))
+                g[name + "/inside_msk"] = ins.numpy().reshape(-1)[:n]
+                g[name + "/rows"] = np.array(n + pad)
+                continue
+            batch = {"RT": cam["RT"][None, None], "Ks": cam["K"][None, None], "msks": board[None, None]}
+            ins = mmsk.prepare_inside_pts(torch.from_numpy(p.copy()).view(1, n, 1, 3), rh.torch_batch(batch))
+            g[name + "/inside_mmsk"] = ins.numpy().reshape(-1)
+            ds = object.__new__(mvm.Dataset)
+            ds.ims = np.zeros((1, 1))
+            ds.Ks, ds.Rs, ds.Ts = cam["K"][None], cam["RT"][None, :, :3], cam["RT"][None, :, 3:]
+            ds.get_mask = lambda i, nv: board
+            g[name + "/inside_mesh"] = ds.prepare_inside_pts(p.copy().reshape(n, 1, 1, 3), 0).reshape(-1)
+    path = os.path.join(OUT, "cull_edges.npz")
+    np.savez_compressed(path, **g)
+    print("cull edges:", {k: (v.shape, v.dtype.str, int(v.sum())) for k, v in g.items() if "/inside" in k}, "->", path,
+          "%.0f KB" % (os.path.getsize(path) / 1024))
+
+
 if __name__ == "__main__":
     torch.manual_seed(0)
-    names = sys.argv[1:] or list(scenes.SCENES) + ["raygen", "raygen_edges", "train", "mmsk", "msk", "mesh", "novel", "trained", "batch2"] + ["bench:" + t for t in scenes.BENCH]
+    names = sys.argv[1:] or list(scenes.SCENES) + ["raygen", "raygen_edges", "cull_edges", "train", "mmsk", "msk", "mesh", "novel", "trained", "batch2"] + ["bench:" + t for t in scenes.BENCH]
     for n in names:
         if n == "raygen":
             run_raygen()
         elif n == "raygen_edges":
             run_raygen_edges()
+        elif n == "cull_edges":
+            run_cull_edges()
         elif n == "train":
             run_train_step()
         elif n == "trained":

@@ -2,7 +2,8 @@
 lines and not from the kernels:
 
   * prepare_inside_pts (lib/datasets/light_stage/multi_view_mesh_dataset.py:117-140) twice — with the reference's float32
-    lib/utils/base_utils.py:17-26 `project` (np.dot in float32: BLAS decides the summation order), and in float64 with np.rint;
+    lib/utils/base_utils.py:17-26 `project` (np.dot in float32: the ascending FMA chain per row, which the device computes too:
+    precision "f32" equals the device at EVERY point, the near band included), and in float64 with np.rint;
   * cv2.dilate with a border x border kernel of ones (:111-113);
   * the NEAR BAND: lattice points whose float64 pixel coordinate in any view lies within BAND px of a half-integer, where a
     float32 projection (any summation order: its error is ~1e-5 px at these image sizes) may round to the other pixel.
@@ -42,12 +43,12 @@ def _pixels(xy, H, W):
 
 
 def project_f32(xyz, K, RT):
-    """lib/utils/base_utils.py:17-26 on float32 arrays"""
-    xyz, K, RT = xyz.astype(np.float32), K.astype(np.float32), RT.astype(np.float32)
-    xyz = np.dot(xyz, RT[:, :3].T) + RT[:, 3:].T
-    xyz = np.dot(xyz, K.T)
-    with np.errstate(divide="ignore", invalid="ignore"):
-        return xyz[:, :2] / xyz[:, 2:]
+    """lib/utils/base_utils.py:17-26 on float32 arrays, its two np.dot written out as the FMA chains they evaluate to
+    (tests/cull_cases.py::project, held to the reference's own answers by tests/golden/cull_edges.npz): no BLAS decides here"""
+    from tests import cull_cases
+
+    x, y = cull_cases.project(dict(K=K, RT=RT), xyz.astype(np.float32), "chain")
+    return np.stack([x, y], axis=1)
 
 
 def project_f64(xyz, K, RT):
@@ -83,13 +84,17 @@ def inside_and_band(axes, msks, Ks, RTs):
 def inside(axes, msks, Ks, RTs, precision="f64"):
     if precision == "f64":
         return inside_and_band(axes, msks, Ks, RTs)[0]
-    pts = lattice_points(axes)
+    return inside_f32_at(lattice_points(axes), msks, Ks, RTs).astype(np.uint8).reshape([len(a) for a in axes])
+
+
+def inside_f32_at(pts, msks, Ks, RTs):
+    """The float32 restatement on the points pts [n,3] alone -> bool [n]: what the device computes, point for point."""
     V, H, W = msks.shape
     ins = np.ones(len(pts), bool)
     for v in range(V):
         x, y = _pixels(project_f32(pts, Ks[v], RTs[v]), H, W)
         ins &= msks[v][y, x] != 0
-    return ins.astype(np.uint8).reshape([len(a) for a in axes])
+    return ins
 
 
 def near_band(axes, msks, Ks, RTs):

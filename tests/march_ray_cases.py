@@ -166,12 +166,13 @@ def integrator_ratios(got, raw, z, ray_d, white_bkgd):
 
 # ------------------------------------------------------------------------------------------------------------------- culling
 def cull_project_f32(p, RT, Kc):
-    """One view's projection of cull_inside, operation for operation in float32: p [..., 3], RT [3, 4], Kc [3, 3] -> the pixel
-    coordinates (x, y) before rounding."""
-    p, RT, Kc = np.asarray(p, F32), np.asarray(RT, F32), np.asarray(Kc, F32)
-    t = [((p[..., 0] * RT[i, 0] + p[..., 1] * RT[i, 1]) + p[..., 2] * RT[i, 2]) + RT[i, 3] for i in range(3)]
-    q = [(t[0] * Kc[i, 0] + t[1] * Kc[i, 1]) + t[2] * Kc[i, 2] for i in range(3)]
-    return q[0] / q[2], q[1] / q[2]
+    """One view's projection of cull_inside (cull_project of nb_march_common.h) in float32, the FMA chains of
+    tests/cull_cases.py::project: p [..., 3], RT [3, 4], Kc [3, 3] -> the pixel coordinates (x, y) before rounding."""
+    from tests import cull_cases
+
+    p = np.asarray(p, F32)
+    x, y = cull_cases.project(dict(RT=RT, K=Kc), p.reshape(-1, 3), "chain")
+    return x.reshape(p.shape[:-1]), y.reshape(p.shape[:-1])
 
 
 def cull_inside_f32(p, RT, Kc, mask):

@@ -235,14 +235,17 @@ def path_case():
 
 
 # ------------------------------------------------------------------------------------------- the kernel's own definition
-def snapped_mask(verts, faces, K, RT, H, W):
-    """include/nb_hip.h's definition of one (frame, view) evaluated on the host: the fp32 projection in nb_cull's operation order
-    (numpy float32 arithmetic rounds each operation as the device does), the snap to 1/256 pixel, integer edge functions
-    -> uint8 [H,W]."""
+def snapped_mask(verts, faces, K, RT, H, W, arith="chain"):
+    """include/nb_hip.h's definition of one (frame, view) evaluated on the host: the fp32 projection in nb_cull's arithmetic
+    (`arith`: the FMA chains of tests/cull_cases.py, which the device is held to; the other names there are the mutants the
+    tests tell apart from it), the snap to 1/256 pixel, integer edge functions -> uint8 [H,W]."""
+    from tests.cull_cases import dot3
+
     f32 = np.float32
     v, K, RT = np.asarray(verts, f32), np.asarray(K, f32), np.asarray(RT, f32)
-    t = [((v[:, 0] * RT[i, 0] + v[:, 1] * RT[i, 1]) + v[:, 2] * RT[i, 2]) + RT[i, 3] for i in range(3)]
-    q = [(t[0] * K[i, 0] + t[1] * K[i, 1]) + t[2] * K[i, 2] for i in range(3)]
+    a = [v[:, 0], v[:, 1], v[:, 2]]
+    t = [dot3(a, RT[i, :3], arith) + RT[i, 3] for i in range(3)]
+    q = [dot3(t, K[i, :], arith) for i in range(3)]
     assert all(a.dtype == f32 for a in t + q)
     with np.errstate(all="ignore"):
         u, w = q[0] / q[2], q[1] / q[2]

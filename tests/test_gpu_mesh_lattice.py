@@ -3,7 +3,8 @@
 
 `inside` is compared at every point OUTSIDE the near band (lattice_ref.BAND: the float64 pixel coordinate within 1e-3 px of a
 half-integer in some view), where a float32 projection may round to the other pixel whatever its summation order; the band may
-not exceed 3 % of the lattice.  Everything else (the gathered points, their order, the dilation, the cube) is compared exactly."""
+not exceed 3 % of the lattice.  INSIDE the band the device is held to the float32 restatement (the FMA chains of tests/cull_cases.py,
+which give the reference's own bitmap at every point of the fixture: tests/test_mesh_lattice_host.py).  Everything else (the gathered points, their order, the dilation, the cube) is compared exactly."""
 import functools
 import os
 import sys
@@ -78,6 +79,13 @@ def _check_outside_band(name, got, c):
     assert band.mean() <= BAND_MAX
     assert got.dtype == np.uint8 and got.shape == ref.shape and set(np.unique(got)) <= {0, 1}
     assert not (diff & ~band).any()
+    # inside the band the float64 restatement does not decide, the float32 one (lattice_ref.project_f32: the FMA chains of
+    # tests/cull_cases.py, which is what the reference's np.dot evaluates to) does: the device equals it at every band point
+    pts = lr.lattice_points(c["axes"])[band.reshape(-1)]
+    chain = lr.inside_f32_at(pts, c["msks"], c["Ks"], c["RT"])
+    miss = int((got.reshape(-1)[band.reshape(-1)].astype(bool) != chain).sum())
+    print("%s: device != float32 chain at %d of the %d band points" % (name, miss, len(pts)))
+    assert miss == 0
 
 
 # ---------------------------------------------------------------------------------------------------------- 1. carve
