@@ -859,6 +859,54 @@ int nb_mask_band(const uint8_t *label, int32_t n_views, int32_t H, int32_t W, in
 int nb_image_undistort(const uint8_t *rgb, const uint8_t *msk, const double *cam, int32_t n_views, int32_t H, int32_t W, int32_t n,
                        int fill, float *img_out, uint8_t *msk_out, void *stream);
 
+/* ---------------------------------------------------------------------------------
+ * An animatable mesh on device — the extracted mesh bound to the SMPL body it clothes, after which it IS an nb_smpl_model with
+ * V = its vertex count: nb_smpl_pose reposes it, nb_mesh_vertex_normals / nb_mesh_render(_attr) draw it, nb_smpl_silhouette
+ * gives clothed cull masks.  replaces: the inverse skin is ppts_to_pts (lib/utils/blend_utils.py:73-82), which the reference
+ * applies to the sample points of its T-pose variant; it has no mesh counterpart.  Plain fp32, "a (+) b" ONE operation rounded
+ * to nearest, none contracted; dot(x, y) = (x0 (*) y0 (+) x1 (*) y1) (+) x2 (*) y2.  No allocation, no synchronisation, everything
+ * on `stream`; the outputs are a function of the inputs alone (the same bits every call, into a dirty buffer too).
+ * nb_mesh_closest — points dev [P,3] fp32, verts dev [V,3] fp32, faces dev [Nf,3] int32 -> face dev [P] int32, bary dev [P,3]
+ *   fp32, dist2 dev [P] fp32: for every point the triangle with the smallest squared distance over ALL triangles, the lower face
+ *   index on a tie.  A face with an index outside 0..V-1 is skipped (the rule of nb_mesh_vertex_normals), and so is a face whose
+ *   dist2 comes out non-finite (collinear corners can divide 0 by 0).  A point with no valid face, or a non-finite point, gets
+ *   face = -1, bary = 0, dist2 = +inf.  Per triangle: the region walk of Ericson, Real-Time Collision Detection 5.1.5, with
+ *   ab = b (-) a, ac = c (-) a, ap = p (-) a, d1 = dot(ab, ap), d2 = dot(ac, ap), ... the vertex, edge and interior regions tested
+ *   in the book's order, edge parameters IEEE divisions (d1 (/) (d1 (-) d3), ...), the interior denom = 1 (/) ((va (+) vb) (+) vc)
+ *   with each of va, vb, vc first replaced by 0 where negative (nothing in exact arithmetic; it bounds v and w whatever rounding
+ *   did to the region tests), v = vb (*) denom, w = vc (*) denom; then bary = ((1 (-) v) (-) w, v, w), q = (a (+) ab (*) v) (+)
+ *   ac (*) w, dist2 = dot(p (-) q, p (-) q).  csrc/nb_mesh_rig.hip writes every line out; tests/mesh_rig_ref.py restates it in
+ *   float32 numpy to the bit.  One thread per point (below 1024 workgroups of 64 points, up to 16 waves share the tiles of a
+ *   workgroup's points and merge under the same order); a prepass (six small launches) sorts the faces into spatially compact tiles
+ *   of 64 with a bounding sphere each, which a wave skips when the sphere's lower bound, taken conservatively in fp32 (the
+ *   source says why), exceeds every lane's current best: the result equals the exhaustive one bit for bit.  flags: 0, or for
+ *   benchmarks NB_CLOSEST_EXHAUSTIVE (no tile is skipped) | NB_CLOSEST_COUNT_TILES (two uint64 at byte 32 of the scratch
+ *   receive the tiles skipped and the tiles met, summed over the waves).  scratch dev, 16-byte aligned:
+ *   nb_mesh_closest_scratch_size(V, Nf) bytes (0 for refused sizes).
+ *   1 <= P, V, Nf and 3 P, 3 V, 3 Nf < 2^31 - 256, else NB_EINVAL.
+ * nb_mesh_rig_bind — one thread per mesh vertex.  model: the BODY; params dev [NB_SMPL_PARAMS]: the bind frame's row; ws dev
+ *   [NB_SMPL_WS_FLOATS]: the row the same nb_smpl_pose call left (A_j - [I|0], rot(Rh)); faces dev [Nf,3]: the body's; points
+ *   dev [P,3]: the mesh vertices, with face, bary of nb_mesh_closest against the posed body.  Outputs, the rig's arrays in
+ *   nb_smpl_model's layout: weights dev [24,P], shapedirs dev [10,3P], v_template dev [P,3]; status dev [4] int32 = {unbound
+ *   vertices, degenerate vertices, 0, 0}.
+ *   w_j = (b0 (*) W[j,v0] (+) b1 (*) W[j,v1]) (+) b2 (*) W[j,v2];  T = [I|0] + sum_j w_j (A_j - [I|0]), j ascending (nb_smpl_pose's
+ *   blend);  y_k = sum_i rot[3i+k] (x_i (-) Th_i), the inverse of its rot . s + Th;  v_shaped = M^-1 ((y (-) t)), M = T[:, :3]
+ *   inverted by adjugate over determinant, t = T[:, 3] (blend_utils.py:79-81);  the shape directions interpolated like w_j;
+ *   v_template = v_shaped (-) sum_l S_l (*) beta_l, l ascending.  Where !(|det M| >= 2^-10) the vertex is bound rigidly to its
+ *   largest-weight joint (the lowest j on a tie): one-hot weights, T = A_j, determinant 1 by construction; status[1] counts
+ *   them.  A vertex with face = -1 gets one-hot weights on joint 0, T = A_0 and zero shape directions; status[0] counts them.
+ *   Pose blend shapes are not transferred: a rig has posedirs = NULL and is driven with new_params = 0; a bind frame posed with
+ *   new_params = 1 has its corrective offsets baked into v_template.  Same size limits, else NB_EINVAL. */
+#define NB_CLOSEST_EXHAUSTIVE 1
+#define NB_CLOSEST_COUNT_TILES 2
+int64_t nb_mesh_closest_scratch_size(int32_t n_verts, int32_t n_faces);
+int nb_mesh_closest(const float *points, const float *verts, const int32_t *faces, int32_t n_points, int32_t n_verts,
+                    int32_t n_faces, int flags, void *scratch, int64_t scratch_bytes, int32_t *face, float *bary, float *dist2,
+                    void *stream);
+int nb_mesh_rig_bind(const nb_smpl_model *model, const float *params, const float *ws, const int32_t *faces, int32_t n_faces,
+                     const float *points, const int32_t *face, const float *bary, int32_t n_points, float *weights,
+                     float *shapedirs, float *v_template, int32_t *status, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

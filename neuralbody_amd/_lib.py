@@ -18,6 +18,7 @@ SAMPLE_MODES = {"h36m": 0, "plain": 1}  # NB_SAMPLE_H36M, NB_SAMPLE_PLAIN
 PAD_MODES = {"zju": 0, "big_box": 1, "snapshot": 2}  # NB_PAD_ZJU, NB_PAD_BIG_BOX, NB_PAD_SNAPSHOT
 SMPL_JOINTS, SMPL_POSE_BASIS, SMPL_BETAS, SMPL_PARAMS, SMPL_WS_FLOATS = 24, 207, 10, 88, 512  # NB_SMPL_*
 CAM_DOUBLES = 12  # NB_CAM_DOUBLES
+CLOSEST_EXHAUSTIVE, CLOSEST_COUNT_TILES = 1, 2  # NB_CLOSEST_*
 FILL_MODES = {None: 0, "black": 1, "white": 2}  # NB_FILL_NONE, NB_FILL_BLACK, NB_FILL_WHITE
 EINTERNAL = -4  # NB_EINTERNAL: what a device output holds when a counted loop gave up
 
@@ -155,6 +156,9 @@ SIGNATURES = {
     "nb_normal_composite": (C.c_int, [_P, _P, _I64, _P, _I64, _I32, _P, _P, _P]),
     "nb_mask_band": (C.c_int, [_P, _I32, _I32, _I32, _I32, _P, _P]),
     "nb_image_undistort": (C.c_int, [_P, _P, C.POINTER(C.c_double), _I32, _I32, _I32, _I32, C.c_int, _P, _P, _P]),
+    "nb_mesh_closest_scratch_size": (_I64, [_I32, _I32]),
+    "nb_mesh_closest": (C.c_int, [_P, _P, _P, _I32, _I32, _I32, C.c_int, _P, _I64, _P, _P, _P, _P]),
+    "nb_mesh_rig_bind": (C.c_int, [C.POINTER(NbSmplModel), _P, _P, _P, _I32, _P, _P, _P, _I32, _P, _P, _P, _P, _P]),
 }
 
 _lib = None

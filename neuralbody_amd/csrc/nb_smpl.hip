@@ -10,6 +10,7 @@
 // Plain fp32, wave64, no atomics, every sum in a fixed order: the same inputs give the same bits.  Products and sums that have to
 // give the same bits in two places (the SMPL-space coordinates of nb_smpl_voxelize's two passes) are written with fmaf.
 #include "nb_common.h"
+#include "nb_smpl_ws.h"
 
 namespace {
 
@@ -17,9 +18,7 @@ constexpr int NJ = NB_SMPL_JOINTS;         // 24
 constexpr int NPF = NB_SMPL_POSE_BASIS;    // 207 = 23 * 9
 constexpr int NB_BETAS = NB_SMPL_BETAS;    // 10
 constexpr int PSTRIDE = NB_SMPL_PARAMS;    // 88 floats per frame: poses 72 | shapes 10 | Rh 3 | Th 3
-// per-frame workspace, floats: A [24][12] (rows of the 3x4 relative transforms, less the identity) | pose feature [207] + 1 pad | rot(Rh) [9] | pad
-constexpr int WS_A = 0, WS_PF = NJ * 12, WS_ROT = WS_PF + NPF + 1, WS_FLOATS = NB_SMPL_WS_FLOATS;
-static_assert(WS_ROT + 9 <= WS_FLOATS, "workspace layout");
+// per-frame workspace: WS_A, WS_PF, WS_ROT, WS_FLOATS of nb_smpl_ws.h
 
 // lbs.py:295-310 as written there: the angle is the norm of the SHIFTED vector, the direction the unshifted vector over it
 __device__ __forceinline__ void rodrigues_f32(const float *__restrict__ r, float *__restrict__ R) {

@@ -1422,6 +1422,78 @@ def mesh_render_attr(vertices, attr, triangles, cams, H, W, out=None, want_face_
                        scratch=scratch, face_id=face_id, depth=depth, _entry="nb_mesh_render_attr")
 
 
+# ------------------------------------------------------------------------------------------- an animatable mesh
+def mesh_closest_scratch(V, Nf, device):
+    """Scratch of mesh_closest against a surface of V vertices and Nf triangles."""
+    return _raster_scratch("nb_mesh_closest_scratch_size", (V, Nf), device, "no closest-point query for V = %d, Nf = %d (each >= 1, "
+                           "3 V and 3 Nf < 2^31 - 256)")
+
+
+def mesh_closest(points, vertices, triangles, scratch=None, face=None, bary=None, dist2=None, exhaustive=False, count_tiles=False):
+    """nb_mesh_closest: points device fp32 [P,3], vertices device fp32 [V,3], triangles device int32 [Nf,3] -> (face int32 [P],
+    bary fp32 [P,3], dist2 fp32 [P]): the closest triangle over all of them (the lower index on a tie), the barycentric
+    coordinates of the closest point and the squared distance; face = -1, bary = 0, dist2 = +inf for a non-finite point or a
+    surface without a valid face.  `exhaustive`, `count_tiles`: for benchmarks (no tile skipped; mesh_closest_tile_counts reads
+    the scratch afterwards).  Nothing is read back."""
+    _req(points, torch.float32, (None, 3), "points")
+    _req(vertices, torch.float32, (None, 3), "vertices")
+    _req(triangles, torch.int32, (None, 3), "triangles")
+    P, V, Nf, dev = int(points.shape[0]), int(vertices.shape[0]), int(triangles.shape[0]), points.device
+    if vertices.device != dev or triangles.device != dev:
+        raise ValueError("points, vertices and triangles live on different devices")
+    if P < 1 or V < 1 or Nf < 1:
+        raise ValueError("points %s, vertices %s or triangles %s is empty" % (tuple(points.shape), tuple(vertices.shape),
+                                                                              tuple(triangles.shape)))
+    if scratch is None:
+        scratch = mesh_closest_scratch(V, Nf, dev)
+    _req(scratch, torch.uint8, (None,), "scratch")
+    face = torch.empty((P,), dtype=torch.int32, device=dev) if face is None else face
+    bary = torch.empty((P, 3), dtype=torch.float32, device=dev) if bary is None else bary
+    dist2 = torch.empty((P,), dtype=torch.float32, device=dev) if dist2 is None else dist2
+    _req(face, torch.int32, (P,), "face")
+    _req(bary, torch.float32, (P, 3), "bary")
+    _req(dist2, torch.float32, (P,), "dist2")
+    flags = (_lib.CLOSEST_EXHAUSTIVE if exhaustive else 0) | (_lib.CLOSEST_COUNT_TILES if count_tiles else 0)
+    with torch.cuda.device(dev):
+        check(_lib.lib().nb_mesh_closest(ptr(points), ptr(vertices), ptr(triangles), P, V, Nf, flags, ptr(scratch), int(scratch.numel()),
+                                         ptr(face), ptr(bary), ptr(dist2), _stream()), "nb_mesh_closest")
+    return face, bary, dist2
+
+
+def mesh_closest_tile_counts(scratch):
+    """(tiles skipped, tiles met) of the last mesh_closest(count_tiles=True) on this scratch, summed over its waves (a read-back)."""
+    c = scratch[32:48].view(torch.int64).cpu()
+    return int(c[0]), int(c[1])
+
+
+def mesh_rig_bind(model, params, ws, triangles, points, face, bary):
+    """nb_mesh_rig_bind: model = the BODY's NbSmplModel, params device fp32 [88] and ws device fp32 [512]: the bind frame's rows of
+    one smpl_pose call, triangles device int32 [Nf,3] the body's, points device fp32 [P,3] with face [P], bary [P,3] of
+    mesh_closest against the posed body -> (weights [24,P], shapedirs [10,3P], v_template [P,3], status int32 [4] = unbound,
+    degenerate, 0, 0), the rig's arrays in the layout of make_smpl_model.  Nothing is read back."""
+    if not isinstance(model, NbSmplModel):
+        raise TypeError("model must be the NbSmplModel of ops.make_smpl_model")
+    _req(params, torch.float32, (_lib.SMPL_PARAMS,), "params")
+    _req(ws, torch.float32, (_lib.SMPL_WS_FLOATS,), "ws")
+    _req(triangles, torch.int32, (None, 3), "triangles")
+    _req(points, torch.float32, (None, 3), "points")
+    P, Nf, dev = int(points.shape[0]), int(triangles.shape[0]), points.device
+    _req(face, torch.int32, (P,), "face")
+    _req(bary, torch.float32, (P, 3), "bary")
+    if P < 1 or Nf < 1:
+        raise ValueError("points %s or triangles %s is empty" % (tuple(points.shape), tuple(triangles.shape)))
+    if any(t.device != dev for t in (params, ws, triangles, face, bary)):
+        raise ValueError("params, ws, triangles, points, face and bary live on different devices")
+    weights = torch.empty((_lib.SMPL_JOINTS, P), dtype=torch.float32, device=dev)
+    shapedirs = torch.empty((_lib.SMPL_BETAS, 3 * P), dtype=torch.float32, device=dev)
+    v_template = torch.empty((P, 3), dtype=torch.float32, device=dev)
+    status = torch.empty((4,), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        check(_lib.lib().nb_mesh_rig_bind(C.byref(model), ptr(params), ptr(ws), ptr(triangles), Nf, ptr(points), ptr(face), ptr(bary), P,
+                                          ptr(weights), ptr(shapedirs), ptr(v_template), ptr(status), _stream()), "nb_mesh_rig_bind")
+    return weights, shapedirs, v_template, status
+
+
 # ------------------------------------------------------------------------------------------- the extracted mesh cleaned and coloured
 MESH_HOOK_ROUNDS = 4  # NB_MESH_HOOK_ROUNDS
 

@@ -274,6 +274,10 @@ class PoseDriver:
         [1,nv,3,3] and RT [1,nv,3,4], the keys RendererMmsk.make_cull reads — the body's silhouettes in those cameras
         (`silhouettes`, enqueued behind the voxelisation, before the wait) dilated by `cull_margin` metres (`cull_border` of the
         frame's can_bounds; one nb_mask_dilate per frame after the wait, nothing else waits)."""
+        if not getattr(self.model, "has_codes", True):
+            raise ops.NbError("frames are the network's input, and the network holds one latent code per vertex of the SMPL body "
+                              "(6890); a %s of %d vertices is geometry only — pose it with `vertices`, draw it with mesh_rig.animate"
+                              % (type(self.model).__name__, self.model.n_verts))
         cull = None if cull_cameras is None else cull_camera_arrays(cull_cameras)
         with self._on_device():
             faces = None if cull is None else self.model.faces_device()  # refuses a model without triangles before any launch
