@@ -907,6 +907,44 @@ int nb_mesh_rig_bind(const nb_smpl_model *model, const float *params, const floa
                      const float *points, const int32_t *face, const float *bary, int32_t n_points, float *weights,
                      float *shapedirs, float *v_template, int32_t *status, void *stream);
 
+/* ---------------------------------------------------------------------------------
+ * Hierarchical sampling behind the march — the per-ray work of the second quadrature of
+ * lib/networks/renderer/volume_renderer.py:82-104,117 between nb_march (coarse pass, raw and weights), nb_decode_points (the new
+ * points) and nb_composite (n_samples + n_importance samples).  One wave per ray, no atomics: the same inputs give the same bits.
+ * Sizes of both entries, else NB_EINVAL: n_samples >= 3 (weights[1:-1] must not be empty), 1 <= n_importance <= 128,
+ * n_samples + n_importance <= 512, 0 <= n_rays < 2^31 (n_rays == 0: NB_OK at once).
+ * nb_importance_sample — replaces sample_pdf (lib/networks/renderer/nerf_net_utils.py:55-90) as volume_renderer.py:86-90 calls it,
+ *   the new points (if_clight_renderer.py:25: o + d * z, :68: d / |d|) and z_std (volume_renderer.py:117).
+ *   ray_o, ray_d, near, far, t_vals, t_rand: the march's (nb_march); the coarse depths z are recomputed exactly as the march forms
+ *   them, the jitter of t_rand included.  weights dev [n_rays, n_samples]: the coarse pass's.
+ *   bins b_j = 0.5 * (z_{j+1} + z_j), j = 0..K with K = n_samples - 2; w_i = weights[i + 1] + 1e-5f, i = 0..K-1; pdf_i = w_i / sum w;
+ *   knots c_0 = 0, c_{i+1} = c_i + pdf_i; for each u: inds = #{j: c_j <= u} (searchsorted side='right'), below = max(inds - 1, 0),
+ *   above = min(K, inds), denom = c_above - c_below, replaced by 1 where < 1e-5, t = (u - c_below) / denom,
+ *   z = b_below + t * (b_above - b_below).  Every operation fp32, rounded once, none contracted; the order of the two sums is written
+ *   out at the top of csrc/nb_importance.hip (lane-strided partial sums and a butterfly; a chunked wave scan).
+ *   u dev: [n_importance] shared by all rays (u_per_ray == 0: torch.linspace(0, 1, n_importance), the reference's det) or
+ *   [n_rays, n_importance] (u_per_ray != 0: torch.rand), any order.
+ *   cull HOST pointer or NULL, as nb_march's: with it keep dev [n_rays, n_importance] uint8 receives 1 where the new point
+ *   projects inside every silhouette (the march's own test), else 0; keep is NULL iff cull is.  pose dev: nb_scene.pose, read
+ *   only when cull->pre_affine (may be NULL otherwise).
+ *   outputs dev: z_coarse [n_rays, n_samples] or NULL; z_fine [n_rays, n_importance]; wpts [n_rays, n_importance, 3] =
+ *   fl32(o + fl32(d * z)); viewdir [n_rays, n_importance, 3] = d / |d| formed in float64 and rounded once;
+ *   z_std [n_rays]: population standard deviation of the ray's z_fine, formed in float64 and rounded once.
+ * nb_importance_merge — replaces torch.sort(torch.cat([z_vals, z_samples], -1), -1) (volume_renderer.py:93) for depths that carry
+ *   their decoded raw: entry e of the concatenation (coarse, then fine) lands at slot #{j: z_j < z_e} + #{j < e: z_j == z_e}, a stable
+ *   sort that needs no sorted input (finite depths).  raw of a fine sample with keep == 0 becomes 0
+ *   (if_clight_renderer_mmsk.py:54-59); keep dev or NULL.  z_coarse [n_rays, n_samples], raw_coarse [n_rays, n_samples, 4],
+ *   z_fine [n_rays, n_importance], raw_fine [n_rays, n_importance, 4] -> z_vals [n_rays, n_samples + n_importance],
+ *   raw [n_rays, n_samples + n_importance, 4]; the three raw arrays 16-byte aligned.
+ * ------------------------------------------------------------------------------- */
+int nb_importance_sample(const float *ray_o, const float *ray_d, const float *near, const float *far, int64_t n_rays,
+                         int32_t n_samples, const float *t_vals, const float *t_rand, const float *weights, int32_t n_importance,
+                         const float *u, int u_per_ray, const nb_cull *cull, const float *pose, float *z_coarse, float *z_fine,
+                         float *wpts, float *viewdir, uint8_t *keep, float *z_std, void *stream);
+int nb_importance_merge(const float *z_coarse, const float *raw_coarse, const float *z_fine, const float *raw_fine,
+                        const uint8_t *keep, int64_t n_rays, int32_t n_samples, int32_t n_importance, float *z_vals, float *raw,
+                        void *stream);
+
 #ifdef __cplusplus
 }
 #endif

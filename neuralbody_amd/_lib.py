@@ -159,6 +159,9 @@ SIGNATURES = {
     "nb_mesh_closest_scratch_size": (_I64, [_I32, _I32]),
     "nb_mesh_closest": (C.c_int, [_P, _P, _P, _I32, _I32, _I32, C.c_int, _P, _I64, _P, _P, _P, _P]),
     "nb_mesh_rig_bind": (C.c_int, [C.POINTER(NbSmplModel), _P, _P, _P, _I32, _P, _P, _P, _I32, _P, _P, _P, _P, _P]),
+    "nb_importance_sample": (C.c_int, [_P, _P, _P, _P, _I64, _I32, _P, _P, _P, _I32, _P, C.c_int, C.POINTER(NbCull), _P, _P, _P, _P,
+                                       _P, _P, _P, _P]),
+    "nb_importance_merge": (C.c_int, [_P, _P, _P, _P, _P, _I64, _I32, _I32, _P, _P, _P]),
 }
 
 _lib = None

@@ -755,12 +755,14 @@ class Network(nn.Module):
             raw[b, idx, -1, 3] = torch.where(sig[idx].abs() < ILL_SIGMA, exact, sig[idx])
         return raw
 
-    def calculate_density_color(self, wpts, viewdir, feature_volume, sp_input):
+    def calculate_density_color(self, wpts, viewdir, feature_volume, sp_input, precision=None):
+        """latent_xyzc.py:91-126.  precision (an extension): 'f32' / 'f16f6' for this call instead of the Network's arithmetic."""
         B = wpts.shape[0]
         if B != 1:
             return torch.cat([self.calculate_density_color(wpts[b:b + 1], viewdir[b:b + 1], frame_volumes(feature_volume, b),
-                                                           frame_sp_input(dict(sp_input, batch_size=B), b)) for b in range(B)], 0)
-        return self._decode(wpts, viewdir, feature_volume, sp_input, False).view(1, -1, 4)
+                                                           frame_sp_input(dict(sp_input, batch_size=B), b), precision=precision)
+                              for b in range(B)], 0)
+        return self._decode(wpts, viewdir, feature_volume, sp_input, False, precision).view(1, -1, 4)
 
     def forward(self, sp_input, grid_coords, viewdir, light_pts):
         """Working equivalent of the reference's (broken, latent_xyzc.py:128-163) forward: `viewdir`

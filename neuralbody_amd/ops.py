@@ -963,6 +963,58 @@ def normal_composite(idx, grad, weights, normal_map=None, normal_acc=None):
     return normal_map, normal_acc
 
 
+# ------------------------------------------------------------------------------------------- hierarchical sampling
+IMPORTANCE_MAX, MERGED_MAX = 128, 512  # nb_importance_sample / nb_importance_merge: n_importance, n_samples + n_importance
+
+
+def importance_sample(ray_o, ray_d, near, far, t_vals, t_rand, weights, u, cull=None, pose=None, want_z_coarse=True):
+    """nb_importance_sample: the importance depths of every ray from the coarse pass's weights [n,S] (sample_pdf, nerf_net_utils.py:55-90,
+    on the midpoints of the march's own depths).  u [N] (shared by all rays: linspace(0, 1, N)) or [n,N] (per ray).  cull: the
+    (NbCull, keepalive) of make_cull — the result then carries keep [n,N] uint8; pose: the 15-float block of make_pose (needed by a
+    pre_affine cull only).  -> dict z_fine [n,N], wpts / viewdir [n,N,3], z_std [n], z_coarse [n,S] (unless want_z_coarse is False),
+    keep or None."""
+    n, S = _march_rays(ray_o, ray_d, near, far, t_vals, t_rand, weights)
+    if u.dim() not in (1, 2):
+        raise ValueError("u is [N] or [n, N], got %s" % (tuple(u.shape),))
+    N = int(u.shape[-1])
+    _req(u, torch.float32, (N,) if u.dim() == 1 else (n, N), "u")
+    dev = ray_o.device
+    out = {"z_fine": torch.empty((n, N), dtype=torch.float32, device=dev),
+           "wpts": torch.empty((n, N, 3), dtype=torch.float32, device=dev),
+           "viewdir": torch.empty((n, N, 3), dtype=torch.float32, device=dev),
+           "z_std": torch.empty((n,), dtype=torch.float32, device=dev),
+           "z_coarse": torch.empty((n, S), dtype=torch.float32, device=dev) if want_z_coarse else None,
+           "keep": torch.empty((n, N), dtype=torch.uint8, device=dev) if cull is not None else None}
+    if pose is not None:
+        _req(pose, torch.float32, (15,), "pose")
+    with torch.cuda.device(dev):
+        check(_lib.lib().nb_importance_sample(ptr(ray_o), ptr(ray_d), ptr(near), ptr(far), n, S, ptr(t_vals), ptr(t_rand), ptr(weights),
+                                              N, ptr(u), 1 if u.dim() == 2 else 0, C.byref(cull[0]) if cull is not None else None,
+                                              ptr(pose), ptr(out["z_coarse"]), ptr(out["z_fine"]), ptr(out["wpts"]), ptr(out["viewdir"]),
+                                              ptr(out["keep"]), ptr(out["z_std"]), _stream()), "nb_importance_sample")
+    return out
+
+
+def importance_merge(z_coarse, raw_coarse, z_fine, raw_fine, keep=None):
+    """nb_importance_merge: z_coarse [n,S] + raw_coarse [n,S,4] and z_fine [n,N] + raw_fine [n,N,4] -> (z_vals [n,S+N], raw [n,S+N,4])
+    sorted by depth, stable (coarse before fine at equal depth); raw = 0 for fine samples with keep [n,N] uint8 == 0."""
+    _req(z_coarse, torch.float32, (None, None), "z_coarse")
+    n, S = z_coarse.shape
+    _req(raw_coarse, torch.float32, (n, S, 4), "raw_coarse")
+    _req(z_fine, torch.float32, (n, None), "z_fine")
+    N = int(z_fine.shape[1])
+    _req(raw_fine, torch.float32, (n, N, 4), "raw_fine")
+    if keep is not None:
+        _req(keep, torch.uint8, (n, N), "keep")
+    dev = z_coarse.device
+    z_vals = torch.empty((n, S + N), dtype=torch.float32, device=dev)
+    raw = torch.empty((n, S + N, 4), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        check(_lib.lib().nb_importance_merge(ptr(z_coarse), ptr(raw_coarse), ptr(z_fine), ptr(raw_fine), ptr(keep), n, S, N, ptr(z_vals),
+                                             ptr(raw), _stream()), "nb_importance_merge")
+    return z_vals, raw
+
+
 class ZeroArena:
     """One zero fill for everything a pass accumulates into (atomics, column sums, scatter targets): `take(shape, dtype)` hands
     out views of a single torch.zeros buffer sized by a planning pass over the same requests (`ZeroArena.plan()` counts)."""

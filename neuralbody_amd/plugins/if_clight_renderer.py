@@ -28,6 +28,8 @@ class _LiveCfg:
     render_normals = property(lambda self: bool(getattr(cfg, "render_normals", False)))
     normal_weight_min = property(lambda self: float(getattr(cfg, "normal_weight_min", 2.0 ** -8)))
     mesh_normals = property(lambda self: str(getattr(cfg, "mesh_normals", "faces")))
+    # hierarchical sampling (volume_renderer.py:82-104; the reference's light-stage configs have no such key: absent = 0 = off)
+    N_importance = property(lambda self: int(getattr(cfg, "N_importance", 0)))
 
 
 class Renderer(_Renderer):

@@ -22,7 +22,7 @@ class RenderConfig:
 
     def __init__(self, N_samples=64, perturb=0.0, raw_noise_std=0.0, white_bkgd=False, H=None, W=None, mesh_th=50.0,
                  mesh_backend="auto", mesh_components="all", mesh_color=False, render_normals=False, normal_weight_min=2.0 ** -8,
-                 mesh_normals="faces"):
+                 mesh_normals="faces", N_importance=0):
         # H, W (optional): image size of the view the rays come from (cfg.H * cfg.ratio in the reference); when
         # batch['mask_at_box'] covers H*W pixels, rays are marched in 8x8 pixel tiles
         self.H, self.W = H, W
@@ -44,6 +44,9 @@ class RenderConfig:
         self.render_normals = bool(render_normals)
         self.normal_weight_min = float(normal_weight_min)
         self.mesh_normals = str(mesh_normals)
+        # hierarchical sampling (lib/config/config.py N_importance, volume_renderer.py:82-104; no light-stage config of the reference sets
+        # it): render() puts this many more samples per ray where the first pass found the surface (`_importance_pass`); 0 = off
+        self.N_importance = int(N_importance)
 
 
 class ColoredMesh(collections.namedtuple("ColoredMesh", "vertices triangles rgb_f rgb_u8 wpts viewdir normals")):
@@ -171,8 +174,14 @@ class Renderer:
 
     # -- if_clight_renderer.py:94-122
     def render(self, batch, t_rand=None, want_raw=False, ray_range=None, feature_volume=None, raw_noise=None, prefetched=None,
-               normals=None):
+               normals=None, n_importance=None, u_rand=None):
         """ray_range = (begin, end) renders a contiguous slice of the rays (multi-GPU sharding).
+        n_importance (None: cfg.N_importance, absent = 0 = off): hierarchical sampling, volume_renderer.py:82-104 with ONE network —
+        that many more samples per ray, drawn from the first pass's weights, decoded and composited together with the first pass's
+        (`_importance_pass`; inference only).  rgb_map / disp_map / acc_map / depth_map are then the second pass's, weights and the new
+        key z_vals are [B,n,N_samples + n_importance], rgb0 / disp0 / acc0 the first pass's maps and z_std [B,n] the spread of the new
+        depths.  u_rand [B,n,n_importance] in [0,1): used instead of torch.rand when cfg.perturb != 0, the way t_rand is (perturb == 0
+        takes linspace(0, 1, n_importance), the reference's det).  With 0 the dict and the launches are what they were.
         normals (None: cfg.render_normals, absent = off): adds normal_map [B,n,3], the surface normal of the density field in world
         axes (unit, or zero where nothing was selected), and normal_acc [B,n], the weight of the samples it blends (`_field_normals`;
         inference only).  Without it the dict and the launches are what they were.
@@ -184,9 +193,23 @@ class Renderer:
         asked_value, asked = normals, bool(normals)  # (by the caller; the cfg key alone leaves a training step as it is)
         if normals is None:
             normals = bool(getattr(self.cfg, "render_normals", False))
+        n_imp = int(getattr(self.cfg, "N_importance", 0) or 0) if n_importance is None else int(n_importance)
+        if n_imp < 0:
+            raise ValueError("n_importance must be >= 0, got %d" % n_imp)
+        if n_imp:
+            if torch.is_grad_enabled() and any(p.requires_grad for p in self.net.parameters()):
+                raise NotImplementedError("hierarchical sampling (n_importance > 0) is inference-only: the second pass has no backward "
+                                          "(wrap the call in torch.no_grad(), as run.py:66,98 does)")
+            if normals:
+                raise NotImplementedError("hierarchical sampling (n_importance > 0) with field normals: the normals are selected by the "
+                                          "first pass's weights and depths, which the second pass replaces; render them separately")
+            if float(self.cfg.raw_noise_std) != 0.0:
+                raise NotImplementedError("hierarchical sampling (n_importance > 0) with raw_noise_std != 0: the reference draws fresh "
+                                          "noise for the merged samples (nerf_net_utils.py:31-35), which the first pass's raw cannot carry")
         if n_batch != 1:
             # (the caller's own value goes down, not the resolved one: the cfg key alone never stops a training step, B > 1 included)
-            return self._render_frames(batch, n_batch, t_rand, want_raw, ray_range, feature_volume, raw_noise, asked_value)
+            return self._render_frames(batch, n_batch, t_rand, want_raw, ray_range, feature_volume, raw_noise, asked_value,
+                                       n_importance, u_rand)
         if torch.is_grad_enabled() and ray_range is None and any(p.requires_grad for p in self.net.parameters()):
             # training step (lib/train/trainers/if_nerf_clight.py:18-36): differentiable HIP path
             from . import training
@@ -227,9 +250,18 @@ class Renderer:
         noisy = self.cfg.raw_noise_std != 0.0
         ret = self.net.render_rays(ray_o[0, b:e].contiguous(), ray_d[0, b:e].contiguous(), near[0, b:e].contiguous(),
                                    far[0, b:e].contiguous(), feature_volume, sp_input, self.cfg.N_samples, t_rand=tr,
-                                   white_bkgd=self.cfg.white_bkgd, want_raw=want_raw or noisy, ray_order=ray_order, cull=cull,
-                                   order_covers_all=covers)
+                                   white_bkgd=self.cfg.white_bkgd, want_raw=want_raw or noisy or bool(n_imp), ray_order=ray_order,
+                                   cull=cull, order_covers_all=covers)
         self.last_ill = getattr(self.net, "last_ill", None)  # header of the march's last-sample fix-up (diagnostics)
+        if n_imp:
+            if float(self.cfg.perturb) == 0.0:  # the reference's det (volume_renderer.py:90)
+                u = self._memo.get("u_det", (n_imp, str(ray_o.device)), lambda: torch.linspace(0.0, 1.0, steps=n_imp).to(ray_o.device))
+            elif u_rand is None:
+                u = torch.rand((e - b, n_imp), device=ray_o.device)
+            else:
+                u = u_rand[0, b:e].float().contiguous()
+            ret = self._importance_pass(ret, n_imp, u, ray_o[0, b:e].contiguous(), ray_d[0, b:e].contiguous(),
+                                        near[0, b:e].contiguous(), far[0, b:e].contiguous(), tr, cull, feature_volume, sp_input, want_raw)
         if noisy:
             # raw_noise_std > 0 (nerf_net_utils.py:31-35; no shipped config): the march delivers `raw`, the noise is added to the
             # densities and the rays are composited again by nb_composite with the z values of the same sampling
@@ -244,6 +276,40 @@ class Renderer:
                 ret["weights"], ray_o[0, b:e].contiguous(), ray_d[0, b:e].contiguous(), near[0, b:e].contiguous(),
                 far[0, b:e].contiguous(), tr, feature_volume, sp_input)
         return {k: v[None] for k, v in ret.items()}
+
+    IMPORTANCE_CHUNK = 1 << 21  # new points per pass of _importance_pass (position, direction and raw: 40 bytes each, 84 MB)
+
+    def _importance_pass(self, coarse, n_imp, u, ray_o, ray_d, near, far, t_rand, cull, feature_volume, sp_input, want_raw):
+        """The second quadrature behind a march that delivered `raw` and `weights` (volume_renderer.py:84-104,117, with one network):
+        nb_importance_sample draws n_imp depths per ray from the first pass's weights (sample_pdf on the midpoints of the march's own
+        depths) and writes their points, Network.calculate_density_color decodes ONLY those (the arithmetic the march used; the first
+        pass's raw is the same field at its own samples), nb_importance_merge sorts both sets by depth — a culled point's raw zeroed, the
+        first pass's last sample, z = far, staying last with the density its fix-up left — and nb_composite integrates S + n_imp samples.
+        u: [n_imp] for all rays or [n, n_imp].  Rays go through in chunks of IMPORTANCE_CHUNK new points, so a large view never holds
+        all of them at once; a ray's result does not depend on the chunking beyond what the decoder's grouping does ('f16f6')."""
+        n, S = coarse["weights"].shape
+        dev = ray_o.device
+        prec = self.net.march_precision()
+        t_vals = self.net.t_vals(S, dev)
+        pose = None
+        if cull is not None and cull[0].pre_affine:  # (the _msk cull carries the point into the snapshot frame through the pose)
+            pose = self.net._pose_block(sp_input["R"], sp_input["Th"], sp_input["bounds"], dev, sp_input.get("_frame_token"))
+        step = max(1, self.IMPORTANCE_CHUNK // n_imp)
+        names = ("rgb_map", "disp_map", "acc_map", "weights", "depth_map", "z_vals", "z_std") + (("raw",) if want_raw else ())
+        parts = {k: [] for k in names}
+        for i in (range(0, n, step) if n else (0,)):
+            sl = slice(i, i + step)
+            smp = ops.importance_sample(ray_o[sl], ray_d[sl], near[sl], far[sl], t_vals, None if t_rand is None else t_rand[sl],
+                                        coarse["weights"][sl], u if u.dim() == 1 else u[sl], cull=cull, pose=pose)
+            raw_fine = self.net.calculate_density_color(smp["wpts"].view(1, -1, 3), smp["viewdir"].view(1, -1, 3), feature_volume,
+                                                        sp_input, precision=prec).view(-1, n_imp, 4)
+            z_vals, raw = ops.importance_merge(smp["z_coarse"], coarse["raw"][sl], smp["z_fine"], raw_fine, smp["keep"])
+            rgb, disp, acc, weights, depth = ops.composite(raw, z_vals, ray_d[sl], self.cfg.white_bkgd)
+            for k, v in zip(names, (rgb, disp, acc, weights, depth, z_vals, smp["z_std"], raw)):
+                parts[k].append(v)
+        ret = {k: (v[0] if len(v) == 1 else torch.cat(v, 0)) for k, v in parts.items()}
+        ret.update(rgb0=coarse["rgb_map"], disp0=coarse["disp_map"], acc0=coarse["acc_map"])
+        return ret
 
     def _field_normals(self, weights, ray_o, ray_d, near, far, t_rand, feature_volume, sp_input):
         """(normal_map [n,3], normal_acc [n]) behind a march: nb_normal_select lists the samples with weights >= cfg.normal_weight_min
@@ -267,7 +333,8 @@ class Renderer:
             grad = self.net.calculate_density_gradient(wpts[None], feature_volume, sp_input)[1][0]
         return ops.normal_composite(idx, grad, weights)
 
-    def _render_frames(self, batch, n_batch, t_rand, want_raw, ray_range, feature_volume, raw_noise, normals=None):
+    def _render_frames(self, batch, n_batch, t_rand, want_raw, ray_range, feature_volume, raw_noise, normals=None, n_importance=None,
+                       u_rand=None):
         """A batch of B > 1 frames (lib/config/config.py:81 defaults train.batch_size to 4; every shipped YAML sets 1): B renders of
         one frame each — differentiable or not — stacked along the batch dimension.  The reference itself cannot run this case (its
         Network pairs ONE set of 6890 vertex codes with the B * 6890 coordinates of the batch, latent_xyzc.py:35-36, which spconv
@@ -282,7 +349,8 @@ class Renderer:
             sub["out_sh"] = out_sh
             fv = None if feature_volume is None else frame_volumes(feature_volume, b)
             outs.append(self.render(sub, t_rand=None if t_rand is None else t_rand[b:b + 1], want_raw=want_raw, ray_range=ray_range,
-                                    feature_volume=fv, raw_noise=None if raw_noise is None else raw_noise[b:b + 1], normals=normals))
+                                    feature_volume=fv, raw_noise=None if raw_noise is None else raw_noise[b:b + 1], normals=normals,
+                                    n_importance=n_importance, u_rand=None if u_rand is None else u_rand[b:b + 1]))
         return {k: torch.cat([o[k] for o in outs], 0) for k in outs[0]}
 
     # -- the encoder of the NEXT frame under the march of this one (no counterpart in the reference, whose render() is one
