@@ -264,6 +264,41 @@ int nb_composite_bwd(const float *raw, const float *z_vals, const float *ray_d, 
                      int32_t n_samples, int white_bkgd, const float *d_rgb_map, const float *d_acc_map,
                      const float *d_depth_map, float *d_raw, void *stream);
 
+/* nb_composite_bwd_maps — the backward of raw2outputs (nerf_net_utils.py:19-49) for ALL five of its outputs: replaces what autograd
+ * does in the reference when a loss reads acc_map (the wrapper's acc_crit, lib/train/trainers/if_nerf_clight.py:16), depth_map,
+ * disp_map or weights.  The arguments of nb_composite_bwd plus d_disp_map dev [n_rays] and d_weights dev [n_rays, n_samples].  Any
+ * of the five cotangents may be NULL, read as 0; at least one must be given (NB_EINVAL otherwise); n_rays == 0: NB_OK at once.
+ * One thread per ray, two sweeps (T_i stashed in d_raw[..., 3] by the first), with c = sigmoid(raw_rgb), B_i = sum_{k>i} w_k dw_k:
+ *   dw_i     = g_rgb . c_i + g_acc + g_depth z_i - [white_bkgd] sum(g_rgb) + d_weights[ray, i]
+ *   d raw_rgb = w_i g_rgb (.) c_i (1 - c_i)
+ *   dalpha_i = T_i dw_i - B_i / (1 - alpha_i + 1e-10)
+ *   dsigma_i = dalpha_i dist_i (1 - alpha_i) [sigma_i > 0]
+ * With only d_rgb_map / d_acc_map / d_depth_map given, d_raw is nb_composite_bwd's bit for bit (the same operations in the same order).
+ * Disparity: disp = 1 / max(1e-10, q) with q = depth / acc (nerf_net_utils.py:42-43).  The first sweep also forms acc = sum w_i and
+ * depth = sum w_i z_i (fp32, in sample order).  Where q > 1e-10 the two scalars become
+ *   g_acc += d_disp / (q acc)      g_depth -= d_disp / (q q acc)
+ * Where q is NOT greater than 1e-10 — a smaller value, a tie, or NaN (acc == 0: every density <= 0, the usual background ray) —
+ * d_disp_map contributes nothing.  Autograd gives NaN there (0 * NaN through depth / acc); this entry gives 0. */
+int nb_composite_bwd_maps(const float *raw, const float *z_vals, const float *ray_d, int64_t n_rays, int32_t n_samples,
+                          int white_bkgd, const float *d_rgb_map, const float *d_acc_map, const float *d_depth_map,
+                          const float *d_disp_map, const float *d_weights, float *d_raw, void *stream);
+
+/* nb_ray_distortion — compactness of a ray's weights; no counterpart in the reference (its floaters are removed from the mesh after
+ * the fact).  It is the distortion loss of Mip-NeRF 360 restated for this renderer's samples: sample i stands for the interval up to
+ * the next sample, as raw2outputs uses it; the last sample is a point at the far end.
+ *   weights, z_vals dev [n_rays, n_samples] (z non-decreasing along a ray) -> loss dev [n_rays], d_weights dev [n_rays, n_samples]
+ *   or NULL (not computed).  Per ray, with span = z[S-1] - z[0]:
+ *   span not greater than 0 (one sample, near == far, NaN): loss = 0 and d_weights = 0.  Otherwise s_i = (z_i - z_0) / span,
+ *   m_i = (s_i + s_{i+1}) / 2 and delta_i = s_{i+1} - s_i for i < S-1, m_{S-1} = s_{S-1} and delta_{S-1} = 0,
+ *     L   = sum_i sum_j w_i w_j |m_i - m_j| + (1/3) sum_i w_i^2 delta_i
+ *     G_k = dL / dw_k = 2 sum_j w_j |m_k - m_j| + (2/3) w_k delta_k
+ *   in O(S) per ray from running sums of w_j and w_j m_j (m is non-decreasing; csrc/nb_ray_loss.hip has the order).  The fp32 inputs
+ *   are converted exactly to float64; s, m, delta and every sum are float64; loss and G are rounded to fp32 once, on store.  No
+ *   atomics: the same inputs give the same bits.  z_vals gets no gradient (sample depths are constants of the training step).
+ *   1 <= n_samples <= 512 (the importance pass's S + N ceiling), n_rays >= 0, else NB_EINVAL; n_rays == 0: NB_OK at once. */
+int nb_ray_distortion(const float *weights, const float *z_vals, int64_t n_rays, int32_t n_samples, float *loss, float *d_weights,
+                      void *stream);
+
 /* Row-major fp32 GEMM C[m,n] = alpha * op(A) op(B) + beta * C on the fp32 matrix cores (v_mfma_f32_32x32x2_f32, exact
  * fp32): the backward of the Conv1d(k=1) layers (latent_xyzc.py:99-121).  lda/ldb/ldc are row strides.  op(A) = A^T
  * (trans_a) is the weight-gradient form dW = dY^T X (split over the long row dimension, fp32 atomics; for M, N >= 32, K >= 1024

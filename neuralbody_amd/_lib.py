@@ -99,6 +99,8 @@ SIGNATURES = {
                            _P, _P, _P, _P, _P, _P, _P, _I64, C.c_int, _P]),
     "nb_composite": (C.c_int, [_P, _P, _P, _I64, _I32, C.c_int, _P, _P, _P, _P, _P, _P]),
     "nb_composite_bwd": (C.c_int, [_P, _P, _P, _I64, _I32, C.c_int, _P, _P, _P, _P, _P]),
+    "nb_composite_bwd_maps": (C.c_int, [_P, _P, _P, _I64, _I32, C.c_int, _P, _P, _P, _P, _P, _P, _P]),
+    "nb_ray_distortion": (C.c_int, [_P, _P, _I64, _I32, _P, _P, _P]),
     "nb_sgemm": (C.c_int, [C.c_int, C.c_int, _I32, _I32, _I32, C.c_float, _P, _I32, _P, _I32, C.c_float, _P, _I32, _P]),
     "nb_gemm_fused": (C.c_int, [C.c_int, C.c_int, _I32, _I32, _I32, C.c_float, _P, _I32, _P, _I32, C.c_float, _P, _I32, _P, _I32, _P, _P]),
     "nb_gemm_variant": (C.c_int, [C.c_int, C.c_int, _I32, _I32, _I32, _P, _I32, _P, _I32]),

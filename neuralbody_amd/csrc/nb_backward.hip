@@ -3,6 +3,7 @@
 // PyTorch autograd through raw2outputs, the Conv1d stack, F.grid_sample and spconv).
 //
 //   nb_composite_bwd   d(rgb_map, acc_map, depth_map) -> d raw            (raw2outputs, nerf_net_utils.py:19-49)
+//   nb_composite_bwd_maps   the same with d disp_map and d weights as well: all five outputs of raw2outputs
 //   nb_sgemm / nb_gemm_fused   row-major fp32 GEMMs of the MLP backward on v_mfma_f32_32x32x2_f32 (exact fp32):
 //                      dX = dY.W with the ReLU mask and the bias-gradient column sums in the epilogue (gemm_rows_kernel),
 //                      dW = dY^T.X over the N = rays x samples rows with a split-K kernel (gemm_tn_kernel)
@@ -57,6 +58,74 @@ __global__ void composite_bwd_kernel(const float *__restrict__ raw, const float 
         const float c0 = 1.f / (1.f + expf(-r[s * 4])), c1 = 1.f / (1.f + expf(-r[s * 4 + 1])),
                     c2 = 1.f / (1.f + expf(-r[s * 4 + 2]));
         const float dw = g0 * c0 + g1 * c1 + g2 * c2 + ga + gd * zz[s] + gw;
+        o[s * 4 + 0] = w * g0 * c0 * (1.f - c0);
+        o[s * 4 + 1] = w * g1 * c1 * (1.f - c1);
+        o[s * 4 + 2] = w * g2 * c2 * (1.f - c2);
+        const float dalpha = Ts * dw - B / (__fadd_rn(e, 1e-10f));
+        o[s * 4 + 3] = sig > 0.f ? dalpha * dist * e : 0.f;
+        B += w * dw;
+    }
+}
+
+// The same backward with the cotangents of ALL five outputs of raw2outputs (nb_composite_bwd_maps); every cotangent may be
+// absent (NULL = 0).  Same operations in the same order as composite_bwd_kernel, so that with only d_rgb / d_acc / d_depth the
+// bits are that kernel's; the additions:
+//   weights cotangent    dw_i += d_weights[ray, i]
+//   disparity cotangent  (DISP instantiation) the forward sweep also forms acc = sum w_i, depth = sum w_i z_i, q = depth / acc
+//                        (nerf_net_utils.py:42-43: disp = 1 / max(1e-10, q)); where q > 1e-10 the scalars in front of the backward
+//                        sweep become ga += gdisp / (q acc), gd -= gdisp / (q q acc); where q is not greater (smaller, a tie, NaN
+//                        from acc == 0) d_disp contributes nothing (autograd gives NaN there)
+template <bool DISP>
+__global__ void composite_bwd_maps_kernel(const float *__restrict__ raw, const float *__restrict__ z,
+                                          const float *__restrict__ ray_d, long long n_rays, int S, int white_bkgd,
+                                          const float *__restrict__ d_rgb, const float *__restrict__ d_acc,
+                                          const float *__restrict__ d_depth, const float *__restrict__ d_disp,
+                                          const float *__restrict__ d_w, float *__restrict__ d_raw) {
+    const long long ray = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (ray >= n_rays) return;
+    const float dx = ray_d[ray * 3], dy = ray_d[ray * 3 + 1], dz = ray_d[ray * 3 + 2];
+    const float dn = sqrtf(__fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz)));
+    const float g0 = d_rgb ? d_rgb[ray * 3] : 0.f, g1 = d_rgb ? d_rgb[ray * 3 + 1] : 0.f, g2 = d_rgb ? d_rgb[ray * 3 + 2] : 0.f;
+    float ga = d_acc ? d_acc[ray] : 0.f, gd = d_depth ? d_depth[ray] : 0.f;
+    const float gw = white_bkgd ? -(g0 + g1 + g2) : 0.f;
+    const float *r = raw + ray * S * 4;
+    const float *zz = z + ray * S;
+    const float *gwt = d_w ? d_w + ray * S : nullptr;
+    float *o = d_raw + ray * S * 4;
+    auto dist_of = [&](int s) { return __fmul_rn((s + 1 < S) ? __fsub_rn(zz[s + 1], zz[s]) : 1e10f, dn); };
+    float T = 1.f, acc = 0.f, depth = 0.f;
+    for (int s = 0; s < S; ++s) {
+        const float alpha = 1.f - expf(-fmaxf(r[s * 4 + 3], 0.f) * dist_of(s));
+        o[s * 4 + 3] = T;
+        if constexpr (DISP) {
+            const float w = alpha * T;
+            acc = __fadd_rn(acc, w);
+            depth = __fadd_rn(depth, __fmul_rn(w, zz[s]));
+        }
+        T = T * (__fadd_rn(__fsub_rn(1.f, alpha), 1e-10f));
+    }
+    if constexpr (DISP) {
+        const float gdisp = d_disp[ray];
+        const float q = depth / acc;
+        if (q > 1e-10f) {
+            ga += gdisp / (q * acc);
+            gd -= gdisp / (q * q * acc);
+        }
+    }
+    float B = 0.f;
+    for (int s = S - 1; s >= 0; --s) {
+        const float sig = r[s * 4 + 3], dist = dist_of(s);
+        const float e = expf(-fmaxf(sig, 0.f) * dist);  // 1 - alpha
+        const float alpha = 1.f - e;
+        const float Ts = o[s * 4 + 3];
+        const float w = alpha * Ts;
+        const float c0 = 1.f / (1.f + expf(-r[s * 4])), c1 = 1.f / (1.f + expf(-r[s * 4 + 1])),
+                    c2 = 1.f / (1.f + expf(-r[s * 4 + 2]));
+        // composite_bwd_kernel's `g0 * c0 + g1 * c1 + g2 * c2 + ga + gd * zz[s] + gw` as the compiler contracts it there, written out:
+        // here the optional loads of g0..g2 make it pair g0 c0 and g2 c2 in a packed multiply instead, which rounds g2 c2 on its own
+        float dw = __fmaf_rn(g2, c2, __fmaf_rn(g0, c0, __fmul_rn(g1, c1)));
+        dw = __fadd_rn(__fmaf_rn(gd, zz[s], __fadd_rn(ga, dw)), gw);
+        if (gwt) dw = __fadd_rn(dw, gwt[s]);
         o[s * 4 + 0] = w * g0 * c0 * (1.f - c0);
         o[s * 4 + 1] = w * g1 * c1 * (1.f - c1);
         o[s * 4 + 2] = w * g2 * c2 * (1.f - c2);
@@ -608,6 +677,25 @@ int nb_composite_bwd(const float *raw, const float *z_vals, const float *ray_d, 
     hipLaunchKernelGGL(composite_bwd_kernel, dim3(nb_ceil_div(n_rays, 64)), dim3(64), 0, (hipStream_t)stream, raw, z_vals,
                        ray_d, (long long)n_rays, n_samples, white_bkgd, d_rgb_map, d_acc_map, d_depth_map, d_raw);
     NB_CHECK_LAUNCH("composite_bwd_kernel");
+    return NB_OK;
+}
+
+int nb_composite_bwd_maps(const float *raw, const float *z_vals, const float *ray_d, int64_t n_rays, int32_t n_samples,
+                          int white_bkgd, const float *d_rgb_map, const float *d_acc_map, const float *d_depth_map,
+                          const float *d_disp_map, const float *d_weights, float *d_raw, void *stream) {
+    NB_REQUIRE(n_rays >= 0 && n_samples >= 1, "nb_composite_bwd_maps: bad sizes");
+    if (n_rays == 0) return NB_OK;
+    NB_REQUIRE(raw && z_vals && ray_d && d_raw, "nb_composite_bwd_maps: NULL pointer");
+    NB_REQUIRE(d_rgb_map || d_acc_map || d_depth_map || d_disp_map || d_weights, "nb_composite_bwd_maps: no cotangent given");
+    if (d_disp_map)
+        hipLaunchKernelGGL(composite_bwd_maps_kernel<true>, dim3(nb_ceil_div(n_rays, 64)), dim3(64), 0, (hipStream_t)stream, raw,
+                           z_vals, ray_d, (long long)n_rays, n_samples, white_bkgd, d_rgb_map, d_acc_map, d_depth_map, d_disp_map,
+                           d_weights, d_raw);
+    else
+        hipLaunchKernelGGL(composite_bwd_maps_kernel<false>, dim3(nb_ceil_div(n_rays, 64)), dim3(64), 0, (hipStream_t)stream, raw,
+                           z_vals, ray_d, (long long)n_rays, n_samples, white_bkgd, d_rgb_map, d_acc_map, d_depth_map, d_disp_map,
+                           d_weights, d_raw);
+    NB_CHECK_LAUNCH("composite_bwd_maps_kernel");
     return NB_OK;
 }
 

@@ -781,6 +781,60 @@ def composite_bwd(raw, z_vals, ray_d, d_rgb_map, white_bkgd=False, d_acc_map=Non
     return d_raw
 
 
+def composite_bwd_maps(raw, z_vals, ray_d, white_bkgd=False, d_rgb_map=None, d_acc_map=None, d_depth_map=None, d_disp_map=None,
+                       d_weights=None):
+    """nb_composite_bwd_maps: d raw [n,S,4] from the cotangents of any of raw2outputs' five outputs (d rgb_map [n,3], d acc_map /
+    d depth_map / d disp_map [n], d weights [n,S]; None = 0, at least one must be given).  A ray whose depth / acc is not greater
+    than 1e-10 (acc == 0 included) takes nothing from d_disp_map."""
+    _req(raw, torch.float32, (None, None, 4), "raw")
+    n, S = raw.shape[:2]
+    _req(z_vals, torch.float32, (n, S), "z_vals")
+    _req(ray_d, torch.float32, (n, 3), "ray_d")
+    for t, shape, nm in ((d_rgb_map, (n, 3), "d_rgb_map"), (d_acc_map, (n,), "d_acc_map"), (d_depth_map, (n,), "d_depth_map"),
+                         (d_disp_map, (n,), "d_disp_map"), (d_weights, (n, S), "d_weights")):
+        if t is not None:
+            _req(t, torch.float32, shape, nm)
+    d_raw = torch.empty_like(raw)
+    check(_lib.lib().nb_composite_bwd_maps(ptr(raw), ptr(z_vals), ptr(ray_d), n, S, 1 if white_bkgd else 0, ptr(d_rgb_map),
+                                           ptr(d_acc_map), ptr(d_depth_map), ptr(d_disp_map), ptr(d_weights), ptr(d_raw), _stream()),
+          "nb_composite_bwd_maps")
+    return d_raw
+
+
+def ray_distortion_raw(weights, z_vals, want_grad=True):
+    """nb_ray_distortion: (loss [n], G [n,S] = d loss / d weights, or None when not wanted) of weights, z_vals [n,S]."""
+    _req(weights, torch.float32, (None, None), "weights")
+    n, S = weights.shape
+    _req(z_vals, torch.float32, (n, S), "z_vals")
+    loss = torch.empty((n,), dtype=torch.float32, device=weights.device)
+    G = torch.empty_like(weights) if want_grad else None
+    check(_lib.lib().nb_ray_distortion(ptr(weights), ptr(z_vals), n, S, ptr(loss), ptr(G), _stream()), "nb_ray_distortion")
+    return loss, G
+
+
+class _RayDistortion(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, weights, z_vals):
+        want = ctx.needs_input_grad[0]  # under no_grad (or for constant weights) G is not computed
+        loss, G = ray_distortion_raw(weights.detach(), z_vals.detach(), want_grad=want)
+        ctx.G = G
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        if ctx.G is None:
+            return None, None
+        return g[:, None] * ctx.G, None  # z_vals: sample depths are constants of the step, as in the reference
+
+
+def ray_distortion(weights, z_vals):
+    """Distortion loss per ray [n] of weights, z_vals [n,S] (include/nb_hip.h: nb_ray_distortion), differentiable in `weights`:
+    the forward's one kernel call also writes G = d loss / d weights, the backward returns g[:, None] * G."""
+    if not torch.is_grad_enabled():
+        return ray_distortion_raw(weights, z_vals, want_grad=False)[0]
+    return _RayDistortion.apply(weights, z_vals)
+
+
 def _mat(t, name):
     if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32 or t.dim() != 2 or \
             (t.shape[1] > 1 and t.stride(1) != 1) or t.stride(0) < t.shape[1]:

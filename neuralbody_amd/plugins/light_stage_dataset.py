@@ -37,6 +37,8 @@ class _LiveCfg:
     n_rounds = 4
     # not a reference key: YAML only (the reference's command line refuses keys its config.py does not define)
     seed = property(lambda self: int(getattr(cfg, "train_ray_seed", 0)))
+    # train_ray_mask: True adds `occupancy` to every train item (the mask loss of plugins/if_nerf_clight.py reads it)
+    ray_mask = property(lambda self: bool(getattr(cfg, "train_ray_mask", False)))
 
 
 def disk_source(data_root, human, ann_file, split, device="cuda:0"):

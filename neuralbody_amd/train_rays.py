@@ -167,12 +167,26 @@ class TrainRaySampler:
         return n_filled, rounds, count_body, count_bound
 
 
+def ray_occupancy(msk, pixel, mode):
+    """Foreground mask at the sampler's pixels, float32 [n]: msk [H,W] uint8 and pixel [n,2] int32 (y, x) on the device ->
+    msk == 1 in mode 'h36m' (the border band 100 is never drawn), msk != 0 in mode 'plain'; rows the sampler left unfilled
+    (pixel = (-1, -1), mask_at_box 0) give 0.  A gather on the device, nothing is read back."""
+    y, x = pixel[:, 0].long(), pixel[:, 1].long()
+    filled = (y >= 0) & (x >= 0)
+    m = msk[y.clamp_min(0), x.clamp_min(0)]
+    fg = (m == 1) if mode == "h36m" else (m != 0)
+    return (fg & filled).to(torch.float32)
+
+
 class TrainDataConfig:
     """The cfg keys the dataset core reads (multi_view_dataset.py:52,78,110,169; if_nerf_data_utils.py:83-84)."""
 
     def __init__(self, N_rand=1024, body_sample_ratio=0.5, face_sample_ratio=0.0, begin_ith_frame=0, frame_interval=1,
                  num_train_frame=1, voxel_size=(0.005, 0.005, 0.005), big_box=False, test_novel_pose=False, mode="h36m",
-                 n_rounds=4, seed=0):
+                 n_rounds=4, seed=0, ray_mask=False):
+        """ray_mask (not a reference key): a train item also carries `occupancy` [N_rand] float32, the foreground mask at each
+        ray's pixel, for silhouette supervision of acc_map (plugins/if_nerf_clight.py: mask_loss_weight)."""
+        self.ray_mask = bool(ray_mask)
         self.N_rand, self.body_sample_ratio, self.face_sample_ratio = int(N_rand), float(body_sample_ratio), face_sample_ratio
         self.begin_ith_frame, self.frame_interval, self.num_train_frame = int(begin_ith_frame), int(frame_interval), int(num_train_frame)
         self.voxel_size, self.big_box, self.test_novel_pose = tuple(voxel_size), bool(big_box), bool(test_novel_pose)
@@ -264,6 +278,8 @@ class TrainRayDataset(torch.utils.data.Dataset):
             s = self._sampler.sample(it["img"], it["msk"], it["K"], it["R"], it["T"], fr["can_bounds"], hull=it["hull"])
             self.last_sample = s
             ret = {k: s[k] for k in ("rgb", "ray_o", "ray_d", "near", "far", "mask_at_box")}
+            if getattr(self.cfg, "ray_mask", False):
+                ret["occupancy"] = ray_occupancy(it["msk"], s["pixel"], self._sampler.mode)
         else:  # if_nerf_data_utils.py:220-230: every pixel's ray, float32 near/far, compacted by mask_at_box
             ray_o, ray_d, near, far, mask, n_rays = ops.raygen(H, W, it["K"], it["R"], it["T"], fr["can_bounds"], self.device)
             n = int(n_rays.item())

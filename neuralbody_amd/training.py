@@ -4,6 +4,7 @@ Forward in training mode decodes the sample points with the activation tap on (`
 F | h1 | h2 | h3 | G | V | PE per point) and composites with `nb_composite`; the backward below consumes the tap:
 
     d rgb_map --nb_composite_bwd--> d raw --MLP backward (fp32 MFMA GEMMs with fused ReLU-mask / bias-sum epilogues)-->
+    (a cotangent on any other map of the dict: nb_composite_bwd_maps instead, all five outputs of raw2outputs)
     parameter gradients + dF --nb_trilinear_bwd--> gradients of the active rows of the four feature volumes
 
 The forward is exact fp32.  The backward's large GEMMs (weight gradients with >= 1024 rows, input gradients with >= 1024 rows
@@ -204,10 +205,12 @@ def _blocks():
 
 class RenderFunction(torch.autograd.Function):
     """Differentiable Renderer.render for the training step (lib/train/trainers/if_nerf_clight.py:18-36): forward and
-    backward are both the HIP path; autograd only carries d rgb_map in and the parameter gradients out."""
+    backward are both the HIP path; autograd only carries the cotangents of the five maps in and the parameter gradients out.
+    `aux`: a dict that receives z_vals [B, n, N_samples], the depths the step composited (the t_rand jitter included): a constant
+    of the step, not an autograd output."""
 
     @staticmethod
-    def forward(ctx, renderer, batch, t_rand, raw_noise, *params):
+    def forward(ctx, renderer, batch, t_rand, raw_noise, aux, *params):
         net, cfg = renderer.net, renderer.cfg
         if not net.training:
             # nb_enc_bn_relu_bwd implements the batch-statistics BatchNorm backward only; in eval() the forward normalises
@@ -240,17 +243,27 @@ class RenderFunction(torch.autograd.Function):
         ctx.renderer, ctx.sp_input, ctx.enc_ctx, ctx.scene = renderer, sp_input, enc_ctx, scene
         ctx.saved = (raw, tap, z, rd, w)
         ctx.n_params = len(params)
-        ctx.mark_non_differentiable(disp, acc, weights, depth)
+        ctx.set_materialize_grads(False)  # an output no loss reads arrives in backward as None, not as a zero tensor
+        aux["z_vals"] = z_vals
         return (rgb.view(n_batch, n_pixel, 3), disp.view(n_batch, n_pixel), acc.view(n_batch, n_pixel),
                 weights.view(n_batch, n_pixel, S), depth.view(n_batch, n_pixel))
 
     @staticmethod
-    def backward(ctx, d_rgb, *_unused):
+    def backward(ctx, d_rgb, d_disp, d_acc, d_weights, d_depth):
         renderer = ctx.renderer
         net, cfg = renderer.net, renderer.cfg
         raw, tap, z, rd, w = ctx.saved
         S = z.shape[1]
-        d_raw = ops.composite_bwd(raw.view(-1, S, 4), z, rd, d_rgb.reshape(-1, 3).float().contiguous(), cfg.white_bkgd)
+        if d_disp is None and d_acc is None and d_weights is None and d_depth is None:
+            if d_rgb is None:  # nothing reached any output: autograd does not call backward then, but a caller may
+                return (None,) * (5 + ctx.n_params)
+            # the reference's loss (if_nerf_clight.py:25): rgb_map alone
+            d_raw = ops.composite_bwd(raw.view(-1, S, 4), z, rd, d_rgb.reshape(-1, 3).float().contiguous(), cfg.white_bkgd)
+        else:
+            cot = lambda t, *shape: None if t is None else t.reshape(*shape).float().contiguous()  # noqa: E731
+            d_raw = ops.composite_bwd_maps(raw.view(-1, S, 4), z, rd, cfg.white_bkgd, d_rgb_map=cot(d_rgb, -1, 3),
+                                           d_acc_map=cot(d_acc, -1), d_depth_map=cot(d_depth, -1), d_disp_map=cot(d_disp, -1),
+                                           d_weights=cot(d_weights, -1, S))
         li = ctx.sp_input["latent_index"]
         # ONE zero fill for every accumulator of the pass (column sums, atomics' targets: ~60 fills and memsets otherwise)
         arena = ops.ZeroArena(ops.ZeroArena.size_of(arena_requests(net, ctx.enc_ctx)), w.device) if USE_ARENA else None
@@ -278,7 +291,7 @@ class RenderFunction(torch.autograd.Function):
             gr = g.get(name)
             out.append(None if gr is None else gr.reshape(p.shape))
         assert len(out) == ctx.n_params
-        return (None, None, None, None) + tuple(out)
+        return (None, None, None, None, None) + tuple(out)
 
 
 # tests/test_gpu_backward.py sets this to a dict to receive the forward's activations (MLP tap, encoder records) so that
@@ -288,7 +301,9 @@ MAX_TAP_BYTES = 32 * 2 ** 30  # activation tap kept for the backward pass (ops.D
 
 
 def render_train(renderer, batch, t_rand=None, raw_noise=None):
-    """Renderer.render with gradients: same output dict, rgb_map carries the autograd graph.  raw_noise: standard-normal
+    """Renderer.render with gradients: the inference dict's five maps, every one of them differentiable (a loss on rgb_map alone
+    runs nb_composite_bwd as before, any other cotangent nb_composite_bwd_maps), plus z_vals [B, n, N_samples]: the depths the step
+    composited, detached (the key the importance pass adds).  raw_noise: standard-normal
     [B, n_rays, N_samples] used when cfg.raw_noise_std != 0 (drawn here when None)."""
     n_points = batch["ray_o"].shape[1] * renderer.cfg.N_samples
     tap_bytes = n_points * ops.DBG_WIDTH * 4
@@ -304,5 +319,6 @@ def render_train(renderer, batch, t_rand=None, raw_noise=None):
             raw_noise = torch.randn((batch["ray_o"].shape[0], batch["ray_o"].shape[1], renderer.cfg.N_samples), device=batch["ray_o"].device)
     else:
         raw_noise = None
-    rgb, disp, acc, weights, depth = RenderFunction.apply(renderer, batch, t_rand, raw_noise, *params)
-    return {"rgb_map": rgb, "disp_map": disp, "acc_map": acc, "weights": weights, "depth_map": depth}
+    aux = {}
+    rgb, disp, acc, weights, depth = RenderFunction.apply(renderer, batch, t_rand, raw_noise, aux, *params)
+    return {"rgb_map": rgb, "disp_map": disp, "acc_map": acc, "weights": weights, "depth_map": depth, "z_vals": aux["z_vals"]}
