@@ -980,6 +980,41 @@ int nb_importance_merge(const float *z_coarse, const float *raw_coarse, const fl
                         const uint8_t *keep, int64_t n_rays, int32_t n_samples, int32_t n_importance, float *z_vals, float *raw,
                         void *stream);
 
+/* ---------------------------------------------------------------------------------
+ * Ray bounds from the posed body: the rays of a rendered camera cut to the body's own depth range instead of its box's.  get_rays
+ * (lib/utils/if_nerf/if_nerf_data_utils.py:8-21) forms ray_d = K^-1 (x, y, 1) rotated to the world without normalising it, so when K's
+ * last row is (0, 0, 1) the point o + t ray_d has camera depth exactly t, the unit of get_near_far's near and far; the ray of pixel
+ * (x, y) passes through the integer point (x, y), the centre of the square nb_smpl_silhouette calls pixel (x, y).  No allocation, no
+ * synchronisation, everything on `stream`; every output is a function of the inputs alone (the same bits every call).
+ * nb_body_depth_range — nb_smpl_silhouette's arguments, projection, snap, triangle rules and conservative coverage (one device
+ *   function projects for both); range dev [F,nv,H,W,2] fp32, 8-byte aligned, a dirty buffer is fine.  A triangle's interval is
+ *   [min, max] of the fp32 camera depths (R v + T).z of its three vertices, the values the projection computes (no interpolation).
+ *   range[...,0] = the smallest lower end over the triangles covering the pixel, range[...,1] = the largest upper end; a pixel no
+ *   triangle covers holds (+inf, -inf).  A (frame, view) that nb_smpl_silhouette declares "does not cull" holds (-inf, +inf) at every
+ *   pixel: it does not bound; the other views are unaffected.  Depths are >= 0.01, so their bits order like signed integers: signed
+ *   atomic min / max on the bits, no finishing pass.  The same limits on F, V, Nf, nv, H, W; scratch dev, 16-byte aligned:
+ *   nb_body_depth_range_scratch_size(F, V, Nf, nv) bytes (0 for refused dimensions).  Five stream operations, as nb_smpl_silhouette.
+ * nb_depth_range_widen — range_in dev [n,H,W,2] -> range_out (another buffer), both 8-byte aligned, no NaN in range_in.  First every
+ *   pixel takes the minimum of the lower ends and the maximum of the upper ends over the border x border window centred on it, pixels
+ *   outside the image ignored (nb_mask_dilate's window; border odd, 1..255): the clothing margin in pixels.  Then every aligned
+ *   tile x tile block (origin pixel (0, 0), edge blocks partial; tile 1, 2, 4, 8 or 16) takes the min / max over its pixels, so that
+ *   the samples of a depth step of nb_march's 8 x 8 ray tile stay on one depth plane.  Both steps only widen an interval.  One launch.
+ * nb_raygen_body — nb_raygen with range dev [H,W,2] (8-byte aligned) and margin (metres, finite, >= 0): for a pixel with nb_raygen's
+ *   fp32 near and far, lo = range0 - margin, hi = range1 + margin (one fp32 operation each), near' = fmaxf(near, lo),
+ *   far' = fminf(far, hi); the pixel is kept iff nb_raygen keeps it and near' < far'.  ray_o, ray_d, the compaction in pixel order,
+ *   mask_at_box, n_rays and the scratch are nb_raygen's; with (-inf, +inf) everywhere every output bit is nb_raygen's.  NB_EINVAL for
+ *   a K whose last row is not exactly (0, 0, 1).
+ * ------------------------------------------------------------------------------- */
+int64_t nb_body_depth_range_scratch_size(int32_t n_frames, int32_t n_verts, int32_t n_faces, int32_t n_views);
+int nb_body_depth_range(const float *verts, const int32_t *faces, const float *cam, int32_t n_frames, int32_t n_verts,
+                        int32_t n_faces, int32_t n_views, int32_t H, int32_t W, void *scratch, int64_t scratch_bytes, float *range,
+                        void *stream);
+int nb_depth_range_widen(const float *range_in, int32_t n, int32_t H, int32_t W, int32_t border, int32_t tile, float *range_out,
+                         void *stream);
+int nb_raygen_body(int32_t H, int32_t W, const double K[9], const double R[9], const double T[3], const float bounds[6],
+                   const float *range, float margin, float *ray_o, float *ray_d, float *near, float *far, uint8_t *mask_at_box,
+                   int32_t *n_rays, void *scratch, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -164,6 +164,11 @@ SIGNATURES = {
     "nb_importance_sample": (C.c_int, [_P, _P, _P, _P, _I64, _I32, _P, _P, _P, _I32, _P, C.c_int, C.POINTER(NbCull), _P, _P, _P, _P,
                                        _P, _P, _P, _P]),
     "nb_importance_merge": (C.c_int, [_P, _P, _P, _P, _P, _I64, _I32, _I32, _P, _P, _P]),
+    "nb_body_depth_range_scratch_size": (_I64, [_I32, _I32, _I32, _I32]),
+    "nb_body_depth_range": (C.c_int, [_P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _P, _I64, _P, _P]),
+    "nb_depth_range_widen": (C.c_int, [_P, _I32, _I32, _I32, _I32, _I32, _P, _P]),
+    "nb_raygen_body": (C.c_int, [_I32, _I32, C.c_double * 9, C.c_double * 9, C.c_double * 3, C.c_float * 6, _P, C.c_float, _P, _P,
+                                 _P, _P, _P, _P, _P, _P]),
 }
 
 _lib = None

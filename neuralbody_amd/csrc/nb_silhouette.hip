@@ -1,5 +1,6 @@
 // nb_silhouette.hip — nb_smpl_silhouette: the posed body's triangles rasterised into a handful of cull cameras, conservatively and
-// exactly, as a stand-in for the training-view masks a pose that was never photographed does not have.
+// exactly, as a stand-in for the training-view masks a pose that was never photographed does not have; and nb_body_depth_range: the
+// same triangles in the same cameras, every pixel given the camera-depth interval of the triangles that cover it.
 //
 // Stands where (zju3dv/neuralbody):
 //   lib/datasets/light_stage/multi_view_perform_dataset.py:105-127  get_mask: the CIHP masks of real images, read from disk
@@ -22,11 +23,12 @@ struct Scratch {
     int *hdr;     // [HDR_FLAGS + F * nv]
     int2 *snap;   // [F * nv, V] snapped pixel coordinates
     int *large;   // [F * nv * Nf] (frame, view, triangle) ids of the triangles one thread does not walk
+    float *depth; // [F * nv, V] camera depths (nb_body_depth_range alone)
     long long hdr_bytes, total_bytes;
 };
 
 // 0 total_bytes: dimensions the entry refuses
-Scratch carve(void *base, long long F, long long V, long long Nf, long long nv) {
+Scratch carve(void *base, long long F, long long V, long long Nf, long long nv, bool with_depth = false) {
     Scratch s = {};
     if (F < 1 || V < 1 || Nf < 1 || nv < 1 || nv > NB_MAX_CULL_VIEWS || F > 65535) return s;
     const long long fv = F * nv;
@@ -38,16 +40,15 @@ Scratch carve(void *base, long long F, long long V, long long Nf, long long nv) 
     s.hdr = (int *)p;
     s.snap = (int2 *)(p + s.hdr_bytes);
     s.large = (int *)(p + s.hdr_bytes + snap_bytes);
-    s.total_bytes = s.hdr_bytes + snap_bytes + large_bytes;
+    s.depth = (float *)(p + s.hdr_bytes + snap_bytes + large_bytes);
+    s.total_bytes = s.hdr_bytes + snap_bytes + large_bytes + (with_depth ? nb_align256(4 * fv * V) : 0);
     return s;
 }
 
-// One workgroup = 256 vertices of one (frame, view): the camera is wave-uniform.
-__global__ __launch_bounds__(256) void sil_project_kernel(const float *__restrict__ verts, const float *__restrict__ cam, int V, int nv,
-                                                          int chunks, int2 *__restrict__ snap, int *__restrict__ flags) {
-    const int fv = blockIdx.x / chunks, v = (blockIdx.x % chunks) * 256 + threadIdx.x;
-    if (v >= V) return;
-    const int f = fv / nv, view = fv % nv;
+// Vertex v of frame f through the camera `view`: the cull's projection, the snap to 1 / SUB pixel and the camera depth (R v + T).z.
+// false: the view does not cull (a vertex nearer than MIN_DEPTH, a projection beyond MAX_PIXEL, NaN); s is then (0, 0)
+__device__ __forceinline__ bool project_snap(const float *__restrict__ verts, const float *__restrict__ cam, int V, int f, int view, int v,
+                                             int2 &s, float &depth) {
     const float *__restrict__ pv = verts + ((size_t)f * V + v) * 3;
     const float p[3] = {pv[0], pv[1], pv[2]};
     float t[3], q[3];
@@ -55,14 +56,44 @@ __global__ __launch_bounds__(256) void sil_project_kernel(const float *__restric
     const float u = __fdiv_rn(q[0], q[2]), w = __fdiv_rn(q[1], q[2]);
     // written so that a NaN anywhere lands on the safe side
     const bool ok = t[2] >= MIN_DEPTH && fabsf(u) <= MAX_PIXEL && fabsf(w) <= MAX_PIXEL;
-    int2 s = {0, 0};
+    s = {0, 0};
     if (ok) {
         s.x = (int)rintf((float)SUB * u);  // |256 u| <= 2^23: exact in fp32, half to even
         s.y = (int)rintf((float)SUB * w);
-    } else {
-        flags[fv] = 1;  // racing stores of the same value
     }
+    depth = t[2];
+    return ok;
+}
+
+// One workgroup = 256 vertices of one (frame, view): the camera is wave-uniform.
+__global__ __launch_bounds__(256) void sil_project_kernel(const float *__restrict__ verts, const float *__restrict__ cam, int V, int nv,
+                                                          int chunks, int2 *__restrict__ snap, int *__restrict__ flags) {
+    const int fv = blockIdx.x / chunks, v = (blockIdx.x % chunks) * 256 + threadIdx.x;
+    if (v >= V) return;
+    int2 s;
+    float depth;
+    if (!project_snap(verts, cam, V, fv / nv, fv % nv, v, s, depth)) flags[fv] = 1;  // racing stores of the same value
     snap[(size_t)fv * V + v] = s;
+}
+
+// the same, the vertex's camera depth kept beside its snapped coordinates
+__global__ __launch_bounds__(256) void range_project_kernel(const float *__restrict__ verts, const float *__restrict__ cam, int V, int nv,
+                                                            int chunks, int2 *__restrict__ snap, float *__restrict__ depth,
+                                                            int *__restrict__ flags) {
+    const int fv = blockIdx.x / chunks, v = (blockIdx.x % chunks) * 256 + threadIdx.x;
+    if (v >= V) return;
+    int2 s;
+    float z;
+    if (!project_snap(verts, cam, V, fv / nv, fv % nv, v, s, z)) flags[fv] = 1;
+    snap[(size_t)fv * V + v] = s;
+    depth[(size_t)fv * V + v] = z;
+}
+
+// range = (+inf, -inf) where the rasteriser will draw, (-inf, +inf) where the view does not bound.  A pixel per thread.
+__global__ __launch_bounds__(256) void range_fill_kernel(const int *__restrict__ flags, long long HW, long long n, float2 *__restrict__ range) {
+    const long long p = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (p >= n) return;
+    range[p] = flags[p / HW] ? make_float2(-INFINITY, INFINITY) : make_float2(INFINITY, -INFINITY);
 }
 
 // out = the flag of its (frame, view): 0 where the rasteriser will draw, 1 where the view does not cull.  16 bytes per thread.
@@ -143,6 +174,46 @@ __global__ __launch_bounds__(256) void sil_large_kernel(SilJob job, unsigned cha
     nbraster::large_pass(job, n, count, large);
 }
 
+// The triangle job of nb_raster.h: triangle g of the (frame, view, triangle) ids, its vertex-depth interval folded into every pixel
+// whose square meets it.  Depths are >= MIN_DEPTH, so their fp32 bits order like signed integers, and so do the bits of the two
+// infinities the fill left: integer atomic min / max, the result free of the order of arrival.
+struct RangeJob : Tri {
+    const int *faces, *flags;
+    const int2 *snap;
+    const float *depth;
+    int Nf, V, H, W;
+    int *out;     // the [F,nv,H,W,2] fp32 range as its bits
+    int fv;       // the triangle's (frame, view), set by setup like the Tri
+    int zlo, zhi; // bits of the smallest and the largest of its three vertex depths
+    __device__ __forceinline__ bool setup(int g) {
+        if (!tri_setup(g, Nf, V, H, W, faces, snap, flags, *this, fv)) return false;
+        const int tri = g - fv * Nf;  // its indices passed tri_setup's check
+        const float *__restrict__ dv = depth + (size_t)fv * V;
+        const float za = dv[faces[3 * (size_t)tri]], zb = dv[faces[3 * (size_t)tri + 1]], zc = dv[faces[3 * (size_t)tri + 2]];
+        zlo = __float_as_int(fminf(za, fminf(zb, zc)));
+        zhi = __float_as_int(fmaxf(za, fmaxf(zb, zc)));
+        return true;
+    }
+    __device__ __forceinline__ void pixel(int x, int y) {
+        if (!covers(x, y)) return;
+        int *__restrict__ r = out + 2 * (((size_t)fv * H + y) * W + x);
+        atomicMin(r, zlo);
+        atomicMax(r + 1, zhi);
+    }
+};
+
+__global__ __launch_bounds__(256) void range_small_kernel(RangeJob job, int *__restrict__ out, int n, int *__restrict__ count,
+                                                          int *__restrict__ large) {
+    job.out = out;  // a parameter for its __restrict__ (nb_raster.h)
+    nbraster::small_pass(job, n, count, large);
+}
+
+__global__ __launch_bounds__(256) void range_large_kernel(RangeJob job, int *__restrict__ out, int n, const int *__restrict__ count,
+                                                          const int *__restrict__ large) {
+    job.out = out;  // a parameter for its __restrict__ (nb_raster.h)
+    nbraster::large_pass(job, n, count, large);
+}
+
 }  // namespace
 
 extern "C" int64_t nb_smpl_silhouette_scratch_size(int32_t F, int32_t V, int32_t Nf, int32_t nv) {
@@ -177,5 +248,39 @@ extern "C" int nb_smpl_silhouette(const float *verts, const int32_t *faces, cons
     NB_CHECK_LAUNCH("nb_smpl_silhouette (triangles)");
     hipLaunchKernelGGL(sil_large_kernel, dim3(nbraster::LARGE_BLOCKS), dim3(256), 0, st, job, out, n_tri, count, s.large);
     NB_CHECK_LAUNCH("nb_smpl_silhouette (large triangles)");
+    return NB_OK;
+}
+
+extern "C" int64_t nb_body_depth_range_scratch_size(int32_t F, int32_t V, int32_t Nf, int32_t nv) {
+    return carve(nullptr, F, V, Nf, nv, true).total_bytes;
+}
+
+extern "C" int nb_body_depth_range(const float *verts, const int32_t *faces, const float *cam, int32_t F, int32_t V, int32_t Nf,
+                                   int32_t nv, int32_t H, int32_t W, void *scratch, int64_t scratch_bytes, float *range, void *stream) {
+    NB_REQUIRE(verts && faces && cam && scratch && range, "nb_body_depth_range: NULL pointer");
+    const Scratch s = carve(scratch, F, V, Nf, nv, true);
+    NB_REQUIRE(s.total_bytes > 0,
+               "nb_body_depth_range: F = %d (1..65535), V = %d, Nf = %d (>= 1), nv = %d (1..%d), F nv V and F nv Nf below 2^31 - 256", F, V,
+               Nf, nv, NB_MAX_CULL_VIEWS);
+    NB_REQUIRE(H >= 1 && W >= 1 && H <= 32768 && W <= 32768, "nb_body_depth_range: H = %d, W = %d (1..32768)", H, W);
+    NB_REQUIRE(scratch_bytes >= s.total_bytes, "nb_body_depth_range: scratch holds %lld bytes, %lld needed", (long long)scratch_bytes,
+               s.total_bytes);
+    NB_REQUIRE(((uintptr_t)scratch & 15) == 0, "nb_body_depth_range: scratch must be 16-byte aligned");
+    NB_REQUIRE(((uintptr_t)range & 7) == 0, "nb_body_depth_range: range must be 8-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    const int fv = F * nv, chunks = nb_ceil_div(V, 256), n_tri = fv * Nf;
+    const long long HW = (long long)H * W, n_px = HW * fv;
+    NB_REQUIRE((n_px + 255) / 256 <= 2147483647ll, "nb_body_depth_range: %lld pixels are too many", n_px);
+    int *flags = s.hdr + HDR_FLAGS, *count = s.hdr + HDR_COUNT;
+    NB_HIP(hipMemsetAsync(s.hdr, 0, (size_t)s.hdr_bytes, st));  // the count and every flag
+    hipLaunchKernelGGL(range_project_kernel, dim3(fv * chunks), dim3(256), 0, st, verts, cam, V, nv, chunks, s.snap, s.depth, flags);
+    NB_CHECK_LAUNCH("nb_body_depth_range (project)");
+    hipLaunchKernelGGL(range_fill_kernel, dim3(nb_ceil_div(n_px, 256)), dim3(256), 0, st, flags, HW, n_px, (float2 *)range);
+    NB_CHECK_LAUNCH("nb_body_depth_range (fill)");
+    const RangeJob job = {{}, faces, flags, s.snap, s.depth, Nf, V, H, W};
+    hipLaunchKernelGGL(range_small_kernel, dim3(nb_ceil_div(n_tri, 256)), dim3(256), 0, st, job, (int *)range, n_tri, count, s.large);
+    NB_CHECK_LAUNCH("nb_body_depth_range (triangles)");
+    hipLaunchKernelGGL(range_large_kernel, dim3(nbraster::LARGE_BLOCKS), dim3(256), 0, st, job, (int *)range, n_tri, count, s.large);
+    NB_CHECK_LAUNCH("nb_body_depth_range (large triangles)");
     return NB_OK;
 }

@@ -127,11 +127,16 @@ class NovelViewRenderer:
     nb_raygen (image_rays) -> renderer.render (any Renderer / RendererMmsk / RendererMsk) -> nb_image_assemble
     (if_nerf_demo.py:15-30).  `H, W` are the reduced image size int(cfg.H * cfg.ratio), int(cfg.W * cfg.ratio)."""
 
-    def __init__(self, renderer, H, W, device="cuda:0", reuse_volumes=False):
+    BODY_KEYS = ("body_verts", "body_faces")  # PoseDriver.frames(body=True): what body_bounds reads of a frame, not part of the batch
+
+    def __init__(self, renderer, H, W, device="cuda:0", reuse_volumes=False, body_bounds=None):
         """reuse_volumes: encode a frame once and reuse its feature volumes for every further view of the same frame
         (same `coord` tensor, out_sh, latent-independent encoder weights).  The reference re-encodes per view
         (if_clight_renderer.py:99-100); the volumes are identical (the encoder is deterministic), only the BatchNorm
-        running-statistics side effect of the skipped passes is lost — off by default."""
+        running-statistics side effect of the skipped passes is lost — off by default.
+        body_bounds: a ray_bounds.BodyBounds: every view's rays are cut to the depth range of the frame's posed body (the frame's
+        body_verts / body_faces, PoseDriver.frames(body=True)) instead of the box's; None: nb_raygen, the box."""
+        self.body_bounds = body_bounds
         self.renderer, self.H, self.W, self.device = renderer, int(H), int(W), torch.device(device)
         self.reuse_volumes = bool(reuse_volumes)
         # render_views: the next view's encoder is enqueued on a second HIP stream before this view's march (Renderer.prefetch)
@@ -148,11 +153,18 @@ class NovelViewRenderer:
         key = (tkey(batch["coord"], batch["out_sh"], net.c.weight, *net.xyzc_net.parameters()), batch.get("frame_token"), net.training)
         return self._memo.get("volumes", key, lambda: net.encode_sparse_voxels(self.renderer.prepare_sp_input(batch)))
 
-    def _launch_rays(self, K, RT, can_bounds):
-        """nb_raygen of one view + an asynchronous 4-byte copy of its ray count into pinned host memory; the event marks the
-        copy, so waiting for it does not wait for anything enqueued later (render_views enqueues it a whole view ahead)."""
+    def _launch_rays(self, K, RT, can_bounds, frame=None):
+        """nb_raygen of one view (with body_bounds: its three entries, bounded by the frame's body) + an asynchronous 4-byte copy of
+        its ray count into pinned host memory; the event marks the copy, so waiting for it does not wait for anything enqueued later
+        (render_views enqueues it a whole view ahead)."""
         RT = np.asarray(RT, np.float64)
-        rays = ops.raygen(self.H, self.W, K, RT[:3, :3], RT[:3, 3], can_bounds, self.device)
+        if self.body_bounds is None:
+            rays = ops.raygen(self.H, self.W, K, RT[:3, :3], RT[:3, 3], can_bounds, self.device)
+        else:
+            missing = [k for k in self.BODY_KEYS if frame is None or k not in frame]
+            if missing:
+                raise KeyError("body_bounds needs the frame's %s: make the frames with PoseDriver.frames(..., body=True)" % " and ".join(missing))
+            rays = self.body_bounds.rays(self.H, self.W, K, RT, can_bounds, frame["body_verts"], frame["body_faces"], self.device)
         slot = self._count_slot = (getattr(self, "_count_slot", -1) + 1) % 4
         if getattr(self, "_count_host", None) is None:
             pin = self.device.type == "cuda"
@@ -171,7 +183,7 @@ class NovelViewRenderer:
         if ev is not None:
             ev.synchronize()
         n = int(host[0])  # the march is launched over exactly n rays
-        batch = dict(frame)
+        batch = {k: v for k, v in frame.items() if k not in NovelViewRenderer.BODY_KEYS}
         batch.update(ray_o=ray_o[None, :n], ray_d=ray_d[None, :n], near=near[None, :n], far=far[None, :n],
                      mask_at_box=mask[None])
         return batch
@@ -181,7 +193,7 @@ class NovelViewRenderer:
         `frame`: dict with device tensors coord [1,V,3] i32, out_sh [1,3] i32, bounds [1,2,3], R [1,3,3], Th [1,*,3],
         latent_index [1] (+ the mask-culling keys for the _mmsk/_msk renderers).  One 4-byte host read per view (the ray
         count); a single call waits for everything enqueued before it — loops over views should use render_views."""
-        return self._finish_batch(self._launch_rays(K, RT, can_bounds), frame)
+        return self._finish_batch(self._launch_rays(K, RT, can_bounds, frame), frame)
 
     def render_views(self, views, bgr=False, scale=1.0):
         """Generator over finished views with the ray generation running ONE VIEW AHEAD: view k + 1's nb_raygen and the copy
@@ -190,7 +202,7 @@ class NovelViewRenderer:
         can enqueue the next view's ~110 encoder launches).  `views`: iterable of (K, RT, can_bounds, frame)."""
         it = iter(views)
         cur = next(it, None)
-        launched = None if cur is None else self._launch_rays(cur[0], cur[1], cur[2])
+        launched = None if cur is None else self._launch_rays(cur[0], cur[1], cur[2], cur[3])
         ticket = None
         while cur is not None:
             batch = self._finish_batch(launched, cur[3])
@@ -198,7 +210,7 @@ class NovelViewRenderer:
             cur_ticket, ticket = ticket, None
             ahead = nxt is not None and self.prefetch_encoder and not self.reuse_volumes
             if nxt is not None:
-                launched = self._launch_rays(nxt[0], nxt[1], nxt[2])
+                launched = self._launch_rays(nxt[0], nxt[1], nxt[2], nxt[3])
             fence = self.renderer.fence(self.device) if ahead else None
             with torch.no_grad():  # the render runs without autograd; the consumer's loop body keeps ITS grad mode (yielding from
                 out = self._render_batch(batch, bgr, scale, None, cur_ticket)  # inside the block would leak no_grad into it)

@@ -1449,6 +1449,96 @@ def smpl_silhouette(verts, faces, RT, K, H, W, out=None, scratch=None):
     return out
 
 
+# ------------------------------------------------------------------------------------------- ray bounds from the posed body
+def body_depth_range_scratch(F, V, Nf, nv, device):
+    """Scratch of body_depth_range for F frames of V vertices and Nf triangles in nv views."""
+    return _raster_scratch("nb_body_depth_range_scratch_size", (F, V, Nf, nv), device, "no depth ranges for F = %d, V = %d, Nf = %d, "
+                           "nv = %d (F 1..65535, nv 1..64, F nv V and F nv Nf < 2^31)")
+
+
+def body_depth_range(verts, faces, RT, K, H, W, out=None, scratch=None):
+    """nb_body_depth_range: the arguments of smpl_silhouette -> device fp32 [F,nv,H,W,2], per pixel the smallest and the largest
+    camera depth of the vertices of the triangles that meet it: (+inf, -inf) where none does, (-inf, +inf) all over a view that does
+    not bound (a vertex nearer than 0.01 m or projecting beyond 32768 px); nothing is read back."""
+    _req(verts, torch.float32, (None, None, 3), "verts")
+    _req(faces, torch.int32, (None, 3), "faces")
+    F, V, Nf, dev = int(verts.shape[0]), int(verts.shape[1]), int(faces.shape[0]), verts.device
+    H, W = int(H), int(W)
+    if F < 1 or V < 1 or Nf < 1:
+        raise ValueError("verts %s or faces %s is empty" % (tuple(verts.shape), tuple(faces.shape)))
+    if not 1 <= H <= 32768 or not 1 <= W <= 32768:
+        raise ValueError("H = %d, W = %d (1..32768)" % (H, W))
+    _on_device(RT, "RT")
+    nv = int(_on_device(K, "K").shape[0])
+    if tuple(RT.shape) != (nv, 3, 4) or tuple(K.shape) != (nv, 3, 3):
+        raise ValueError("RT %s, K %s: expected [%d,3,4] and [%d,3,3]" % (tuple(RT.shape), tuple(K.shape), nv, nv))
+    if faces.device != dev or RT.device != dev or K.device != dev:
+        raise ValueError("verts, faces, RT and K live on different devices")
+    cam = _cull_cams(RT, K, nv)
+    if scratch is None:
+        scratch = body_depth_range_scratch(F, V, Nf, nv, dev)
+    _req(scratch, torch.uint8, (None,), "scratch")
+    if out is None:
+        out = torch.empty((F, nv, H, W, 2), dtype=torch.float32, device=dev)
+    _req(out, torch.float32, (F, nv, H, W, 2), "out")
+    with torch.cuda.device(dev):
+        check(_lib.lib().nb_body_depth_range(ptr(verts), ptr(faces), ptr(cam), F, V, Nf, nv, H, W, ptr(scratch), int(scratch.numel()),
+                                             ptr(out), _stream()), "nb_body_depth_range")
+    return out
+
+
+def depth_range_widen(ranges, border=1, tile=1, out=None):
+    """nb_depth_range_widen: device fp32 [...,H,W,2] depth ranges (no NaN) -> a new tensor of the same shape: every pixel takes the
+    min of the lower and the max of the upper ends over its border x border window (odd, 1..255; outside the image ignored), then
+    every aligned tile x tile block (1, 2, 4, 8 or 16; origin pixel (0, 0)) the min / max over its pixels."""
+    _req(ranges, torch.float32, name="ranges")
+    if ranges.dim() < 3 or ranges.shape[-1] != 2 or ranges.numel() == 0:
+        raise ValueError("ranges must be a non-empty [...,H,W,2], got %s" % (tuple(ranges.shape),))
+    border, tile = int(border), int(tile)
+    if border < 1 or border % 2 == 0 or border > 255:
+        raise ValueError("border must be odd, 1..255, got %d" % border)
+    if tile not in (1, 2, 4, 8, 16):
+        raise ValueError("tile must be 1, 2, 4, 8 or 16, got %d" % tile)
+    H, W = int(ranges.shape[-3]), int(ranges.shape[-2])
+    if out is None:
+        out = torch.empty_like(ranges)
+    _req(out, torch.float32, tuple(ranges.shape), "out")
+    if out.data_ptr() == ranges.data_ptr():
+        raise ValueError("out must be another tensor than ranges")
+    with torch.cuda.device(ranges.device):
+        check(_lib.lib().nb_depth_range_widen(ptr(ranges), ranges.numel() // (2 * H * W), H, W, border, tile, ptr(out), _stream()),
+              "nb_depth_range_widen")
+    return out
+
+
+def raygen_body(H, W, K, R, T, bounds, depth_range, margin=0.0):
+    """nb_raygen_body: raygen's host arguments, depth_range device fp32 [H,W,2] (body_depth_range of the SAME camera, widened) and
+    margin in metres: near = max(near, range0 - margin), far = min(far, range1 + margin), a pixel kept iff raygen keeps it and
+    near < far.  K's last row must be (0, 0, 1).  Returns raygen's 6-tuple on depth_range's device."""
+    import numpy as np
+
+    H, W = int(H), int(W)
+    _req(depth_range, torch.float32, (H, W, 2), "depth_range")
+    device = depth_range.device
+    K = np.asarray(K, np.float64).reshape(9)
+    R = np.asarray(R, np.float64).reshape(9)
+    T = np.asarray(T, np.float64).reshape(3)
+    b = np.asarray(bounds, np.float32).reshape(6)
+    n = H * W
+    ray_o = torch.empty((n, 3), dtype=torch.float32, device=device)
+    ray_d = torch.empty((n, 3), dtype=torch.float32, device=device)
+    near = torch.empty(n, dtype=torch.float32, device=device)
+    far = torch.empty(n, dtype=torch.float32, device=device)
+    mask = torch.empty(n, dtype=torch.uint8, device=device)
+    n_rays = torch.zeros(1, dtype=torch.int32, device=device)
+    scratch = scan_scratch(n, device)
+    with torch.cuda.device(device):
+        check(_lib.lib().nb_raygen_body(H, W, (C.c_double * 9)(*K), (C.c_double * 9)(*R), (C.c_double * 3)(*T), (C.c_float * 6)(*b),
+                                        ptr(depth_range), float(margin), ptr(ray_o), ptr(ray_d), ptr(near), ptr(far), ptr(mask),
+                                        ptr(n_rays), ptr(scratch), _stream()), "nb_raygen_body")
+    return ray_o, ray_d, near, far, mask, n_rays
+
+
 # ------------------------------------------------------------------------------------------- pictures of an extracted mesh
 MESH_CAM_FLOATS = 24  # NB_MESH_CAM_FLOATS: affine 3 x 4 | normal rotation 3 x 3 | 3 of padding
 

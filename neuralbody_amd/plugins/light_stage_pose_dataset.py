@@ -12,6 +12,10 @@ and, in the YAML (the reference's command line refuses keys its config.py does n
     cull_views: [0, 6, 12, 18] # default []: no culling.  Cameras of the annotations whose silhouettes of the posed body are
                                # rasterised on the device; the items then hold msks / Ks / RT for the _mmsk renderer
     cull_margin: 0.05          # metres the silhouettes are dilated by (clothing, hair); the default is the box padding
+    ray_bounds: body           # default box: every ray of the SMPL box, near / far its entry and exit.  body: near / far cut to the
+                               # posed body's depth range in the rendered camera, rays beside the body dropped (ray_bounds.py)
+    ray_bounds_margin: 0.05    # metres kept around the body's surface, in depth and in the image
+    ray_bounds_tile: 8         # pixels: the blocks that share one interval (1, 2, 4, 8, 16; 8 is the march's ray tile)
 """
 import os
 import sys
@@ -37,6 +41,9 @@ class _LiveCfg:
     smpl_new_params = property(lambda self: bool(getattr(cfg, "smpl_new_params", "new" in str(getattr(cfg, "params", "params")))))
     cull_views = property(lambda self: tuple(int(v) for v in getattr(cfg, "cull_views", ())))
     cull_margin = property(lambda self: float(getattr(cfg, "cull_margin", 0.05)))
+    ray_bounds = property(lambda self: str(getattr(cfg, "ray_bounds", "box")))
+    ray_bounds_margin = property(lambda self: float(getattr(cfg, "ray_bounds_margin", 0.05)))
+    ray_bounds_tile = property(lambda self: int(getattr(cfg, "ray_bounds_tile", 8)))
 
 
 def disk_source(data_root, human, ann_file):

@@ -266,21 +266,23 @@ class PoseDriver:
             nv = Ks.shape[0]
             return ops.smpl_silhouette(verts, faces, cam[:12 * nv].view(nv, 3, 4), cam[12 * nv:].view(nv, 3, 3), H, W)
 
-    def frames(self, poses, shapes, Rh, Th, latent_index, new_params=False, cull_cameras=None, cull_margin=0.05):
+    def frames(self, poses, shapes, Rh, Th, latent_index, new_params=False, cull_cameras=None, cull_margin=0.05, body=False):
         """-> [(frame, can_bounds)] * F.  `frame`: device tensors coord [1,V,3] i32, out_sh [1,3] i32, bounds [1,2,3], R [1,3,3],
         Th [1,1,3], latent_index [1] (views of the call's [F,...] tensors); `can_bounds`: float32 [2,3] on the host, what
         nb_raygen needs of the frame.  One upload, three launches, one wait: for the event behind the summary's copy.
         `cull_cameras` = (Ks [nv,3,3], RTs [nv,3,4] or [nv,4,4], H, W): every frame also holds msks [1,nv,H,W] uint8, Ks
         [1,nv,3,3] and RT [1,nv,3,4], the keys RendererMmsk.make_cull reads — the body's silhouettes in those cameras
         (`silhouettes`, enqueued behind the voxelisation, before the wait) dilated by `cull_margin` metres (`cull_border` of the
-        frame's can_bounds; one nb_mask_dilate per frame after the wait, nothing else waits)."""
+        frame's can_bounds; one nb_mask_dilate per frame after the wait, nothing else waits).
+        `body`: every frame also holds body_verts [1,V,3] (a view of the posed world vertices, no copy) and body_faces [Nf,3]
+        (the model's triangles): what ray_bounds.BodyBounds bounds a view's rays by (NovelViewRenderer(body_bounds=...))."""
         if not getattr(self.model, "has_codes", True):
             raise ops.NbError("frames are the network's input, and the network holds one latent code per vertex of the SMPL body "
                               "(6890); a %s of %d vertices is geometry only — pose it with `vertices`, draw it with mesh_rig.animate"
                               % (type(self.model).__name__, self.model.n_verts))
         cull = None if cull_cameras is None else cull_camera_arrays(cull_cameras)
         with self._on_device():
-            faces = None if cull is None else self.model.faces_device()  # refuses a model without triangles before any launch
+            faces = None if cull is None and not body else self.model.faces_device()  # refuses a model without triangles before any launch
             native, _ = self.model.native()
             params, latent, cams = self._upload(poses, shapes, Rh, Th, latent_index, cull)
             F = int(params.shape[0])
@@ -305,17 +307,20 @@ class PoseDriver:
                      "R": vox["R"][f:f + 1], "Th": params[f:f + 1, None, 85:88], "latent_index": latent[f:f + 1]}
             if cull is not None:
                 frame.update(msks=msks[f:f + 1], Ks=cams[1][None], RT=cams[0][None])
+            if body:
+                frame.update(body_verts=verts[f:f + 1], body_faces=faces)
             out.append((frame, can_bounds[f]))
         return out
 
-    def views(self, cameras, poses, shapes, Rh, Th, latent_index, new_params=False, cull_cameras=None, cull_margin=0.05):
+    def views(self, cameras, poses, shapes, Rh, Th, latent_index, new_params=False, cull_cameras=None, cull_margin=0.05, body=False):
         """Generator of (K, RT, can_bounds, frame) for NovelViewRenderer.render_views.  `cameras`: a list of (K, RT) pairs, one per
         frame, or a list of ONE pair that every frame is seen by.  All frames are made by one call of `frames` before the
-        first view is yielded.  `cull_cameras`, `cull_margin`: those of `frames`; the frames then feed a RendererMmsk."""
+        first view is yielded.  `cull_cameras`, `cull_margin`, `body`: those of `frames`; the frames then feed a RendererMmsk, or a
+        NovelViewRenderer with body_bounds."""
         cameras = list(cameras)
         if any(len(c) != 2 for c in cameras):
             raise ValueError("cameras must be a list of (K, RT) pairs")
-        made = self.frames(poses, shapes, Rh, Th, latent_index, new_params, cull_cameras, cull_margin)
+        made = self.frames(poses, shapes, Rh, Th, latent_index, new_params, cull_cameras, cull_margin, body)
         if len(cameras) not in (1, len(made)):
             raise ValueError("%d cameras for %d frames (one per frame, or one for all)" % (len(cameras), len(made)))
         for f, (frame, can_bounds) in enumerate(made):
@@ -326,13 +331,23 @@ class PoseDriver:
 # ------------------------------------------------------------------------------------------- dataset core
 class PoseDataConfig:
     """The cfg keys the dataset core reads, plus its own (`smpl_new_params`; `cull_views`, the camera indices of the annotations
-    whose silhouettes cull the items, empty = none; `cull_margin` in metres; the model comes in as an object)."""
+    whose silhouettes cull the items, empty = none; `cull_margin` in metres; `ray_bounds`: 'box' (nb_raygen) or 'body' (the rays cut
+    to the posed body's depth range, ray_bounds.BodyBounds, with `ray_bounds_margin` metres and `ray_bounds_tile` pixels; the model
+    comes in as an object)."""
 
     def __init__(self, begin_ith_frame=0, frame_interval=1, num_train_frame=1, voxel_size=(0.005, 0.005, 0.005), big_box=False,
-                 smpl_new_params=False, cull_views=(), cull_margin=0.05):
+                 smpl_new_params=False, cull_views=(), cull_margin=0.05, ray_bounds="box", ray_bounds_margin=0.05, ray_bounds_tile=8):
         self.begin_ith_frame, self.frame_interval, self.num_train_frame = int(begin_ith_frame), int(frame_interval), int(num_train_frame)
         self.voxel_size, self.big_box, self.smpl_new_params = tuple(voxel_size), bool(big_box), bool(smpl_new_params)
         self.cull_views, self.cull_margin = tuple(int(v) for v in cull_views), float(cull_margin)
+        self.ray_bounds, self.ray_bounds_margin, self.ray_bounds_tile = ray_bounds_mode(ray_bounds), float(ray_bounds_margin), int(ray_bounds_tile)
+
+
+def ray_bounds_mode(name):
+    """The YAML key `ray_bounds`: 'box' or 'body'."""
+    if name not in ("box", "body"):
+        raise ValueError("ray_bounds must be 'box' or 'body', got %r" % (name,))
+    return name
 
 
 class MemoryPoseSource:
@@ -395,7 +410,8 @@ class LightStagePoseSource:
 class PoseFrameDataset(torch.utils.data.Dataset):
     """Item i = frame begin_ith_frame + i * frame_interval, made from its SMPL parameters and seen by the source's camera: the
     batch dict Renderer.render consumes (before collation), all device tensors, with every pixel's ray from nb_raygen.  With
-    cfg.cull_views the item also holds msks [nv,H,W], Ks [nv,3,3], RT [nv,3,4]: what RendererMmsk culls by."""
+    cfg.cull_views the item also holds msks [nv,H,W], Ks [nv,3,3], RT [nv,3,4]: what RendererMmsk culls by.  With cfg.ray_bounds
+    'body' the rays, near / far and mask_at_box are those of ray_bounds.BodyBounds: cut to the posed body's depth range."""
 
     def __init__(self, source, model, cfg, device="cuda:0"):
         super().__init__()
@@ -416,9 +432,18 @@ class PoseFrameDataset(torch.utils.data.Dataset):
         driver = PoseDriver(self.model, cfg.voxel_size, "big_box" if cfg.big_box else "zju", self.device)
         cull_views = tuple(getattr(cfg, "cull_views", ()))
         cull = src.cull_cameras(cull_views) if cull_views else None
+        body = ray_bounds_mode(getattr(cfg, "ray_bounds", "box")) == "body"
         (frame, can_bounds), = driver.frames(p["poses"], p["shapes"], p["Rh"], p["Th"], self.latent_index(index), cfg.smpl_new_params,
-                                             cull, float(getattr(cfg, "cull_margin", 0.05)))
-        ray_o, ray_d, near, far, mask, n_rays = ops.raygen(src.H, src.W, src.K, src.R, src.T, can_bounds, self.device)
+                                             cull, float(getattr(cfg, "cull_margin", 0.05)), body)
+        if body:
+            from .ray_bounds import BodyBounds
+
+            RT = np.concatenate([np.asarray(src.R, np.float64).reshape(3, 3), np.asarray(src.T, np.float64).reshape(3, 1)], axis=1)
+            bounds = BodyBounds(float(getattr(cfg, "ray_bounds_margin", 0.05)), int(getattr(cfg, "ray_bounds_tile", 8)))
+            ray_o, ray_d, near, far, mask, n_rays = bounds.rays(src.H, src.W, src.K, RT, can_bounds, frame["body_verts"],
+                                                                frame["body_faces"], self.device)
+        else:
+            ray_o, ray_d, near, far, mask, n_rays = ops.raygen(src.H, src.W, src.K, src.R, src.T, can_bounds, self.device)
         n = int(n_rays.item())
         ret = {"ray_o": ray_o[:n], "ray_d": ray_d[:n], "near": near[:n], "far": far[:n], "mask_at_box": mask.view(torch.bool),
                "coord": frame["coord"][0], "out_sh": frame["out_sh"][0], "bounds": frame["bounds"][0], "R": frame["R"][0],
