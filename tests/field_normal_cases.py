@@ -198,8 +198,10 @@ def chain_f64(sd, h1, h2, h3):
 
 # ------------------------------------------------------------------------------------------------------------------------ C
 @functools.lru_cache(maxsize=None)
-def e2e_reference(name):
-    """-> dict(wpts fp32 [1024, 3], sigma64 [1024], g64 [1024, 3], keep bool [1024], vols: the oracle's fp32 volumes (NCDHW tensors),
+def e2e_reference(name, voxel_size=None, first_ray=0):
+    """`voxel_size` (dhw, None: the golden scenes' 5 mm cube): the scene's body voxelised, and the oracle's grid coordinates formed, at
+    that size.  `first_ray`: the sixteen rays are first_ray + E2E_RAYS.
+    -> dict(wpts fp32 [1024, 3], sigma64 [1024], g64 [1024, 3], keep bool [1024], vols: the oracle's fp32 volumes (NCDHW tensors),
     out_sh, recipe, sd, batch, h: the float64 activations h1, h2, h3 [1024, 256], gn: the float64 normalised coordinates) of a golden scene"""
     import torch
 
@@ -207,19 +209,21 @@ def e2e_reference(name):
     from tests import helpers as H
     from tests.golden import scenes
 
-    r, sd, body, batch, cam, _ = scenes.build(name)
+    r, sd, body, batch, cam, _ = scenes.build(name, voxel_size)
     sdt, vols, out_sh = H.oracle_volumes(sd, batch, r["mode"] == "train")
     S = 64
+    rays = slice(E2E_RAYS.start + first_ray, E2E_RAYS.stop + first_ray, E2E_RAYS.step)
     t = np.linspace(0.0, 1.0, S, dtype=F32)
-    z = R.z_vals_f32(batch["near"][0][E2E_RAYS], batch["far"][0][E2E_RAYS], t)
-    wpts = R.sample_points_f32(batch["ray_o"][0][E2E_RAYS], batch["ray_d"][0][E2E_RAYS], z)[0].reshape(-1, 3)
+    z = R.z_vals_f32(batch["near"][0][rays], batch["far"][0][rays], t)
+    wpts = R.sample_points_f32(batch["ray_o"][0][rays], batch["ray_d"][0][rays], z)[0].reshape(-1, 3)
     assert wpts.shape == (1024, 3)
     sd64 = orc.tensor_state_dict(sd, dtype=torch.float64)
     vols64 = [v.double() for v in vols]
     sp = {k: torch.from_numpy(np.asarray(batch[k])).double() for k in ("R", "Th", "bounds")}
     sp["out_sh"] = out_sh
     p = torch.from_numpy(wpts.astype(np.float64))[None].requires_grad_(True)
-    gcoord = orc.get_grid_coords(orc.pts_to_can_pts(p, sp["R"], sp["Th"]), sp["bounds"], out_sh, (0.005,) * 3)[:, None, None]
+    gcoord = orc.get_grid_coords(orc.pts_to_can_pts(p, sp["R"], sp["Th"]), sp["bounds"], out_sh,
+                                 (0.005,) * 3 if voxel_size is None else tuple(voxel_size))[:, None, None]
     x = orc.interpolate_features(gcoord, vols64)
     near_zero = torch.zeros(1024, dtype=torch.bool)
     hs = []

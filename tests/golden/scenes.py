@@ -33,11 +33,12 @@ N_PROBES = 160
 RAW_RAY_STRIDE = 8
 
 
-def build(name):
-    """-> (recipe, state_dict_np, body, batch_np, cam(K,R,T,H,W), t_rand or None)"""
+def build(name, voxel_size=None):
+    """-> (recipe, state_dict_np, body, batch_np, cam(K,R,T,H,W), t_rand or None).  `voxel_size` (dhw): the body voxelised at another
+    size than the fixtures' 5 mm cube (the golden files hold the default only)."""
     r = SCENES[name]
     sd = syn.make_weights(r["weights_seed"], num_train_frame=r["num_train_frame"], **r.get("weights_kw", {}))
-    body = syn.make_body(**r["body"])
+    body = syn.make_body(**r["body"], **({} if voxel_size is None else {"voxel_size": tuple(voxel_size)}))
     c = r["cam"]
     K, R, T = syn.make_camera(body, c["H"], c["W"], focal_factor=c["focal_factor"], distance=c["distance"])
     ray_o, ray_d, near, far, mask = syn.host_image_rays(c["H"], c["W"], K, R, T, body["can_bounds"])

@@ -8,7 +8,9 @@ over lbs.py:142-233, 280-378; return_verts=True, scale=1), written from the form
     v'       = (sum_j W[v,j] A_j) . (v_posed, 1),   world = v' . rot(Rh)^T + Th
 
 `forward(model, ..., dtype)` evaluates them in float64 (the tests' reference) or float32 (the host frame tools/bench_smpl_pose.py
-times).  The model arrays carry the reference pickle's names and shapes."""
+times).  The model arrays carry the reference pickle's names and shapes.
+
+`voxelize_f32` restates nb_smpl_voxelize operation by operation (and names its mutants): see the section at the end."""
 import numpy as np
 
 SMPL_PARENTS = [-1, 0, 0, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 9, 9, 12, 13, 14, 16, 17, 18, 19, 20, 21]
@@ -184,3 +186,53 @@ def voxel_case_check(verts, Rh, Th, pad):
     m = np.mod(raw, 32.0)
     band = float(near_band(c64).mean())
     return {"raw": np.round(raw, 2), "band": band, "ok": bool(np.all((m >= 2.0) & (m <= 30.0)) and band <= 0.01)}
+
+
+# ------------------------------------------------------------------------------------------- the voxeliser, operation by operation
+# What nb_smpl_voxelize computes, in its own order (include/nb_hip.h, the header of csrc/nb_smpl.hip), so that the device can be held
+# to it at EVERY coordinate, the ones next to a half-integer included:
+#   d = fl32(v - Th);  s_i = fma(d2, R[2,i], fma(d1, R[1,i], fl32(d0 R[0,i])));  lo, hi = min, max over the vertices;
+#   the pad as one float32 operation on each (an unpadded axis adds 0);  coord (dhw) = rint(float64(fl32(s - lo)) / vs), half to even;
+#   out_sh (dhw) = (ceil(float64(fl32(hi - lo)) / vs) | 31) + 1;  summary = can_bounds' six floats bit-cast | out_sh.
+# The others are MUTANTS: what a careless rewrite would compute instead.  tests/voxelize_cases.py holds the cases that tell them apart.
+VOXELIZERS = {
+    "exact": {},
+    "vs_reversed": dict(reverse_vs=True),      # voxel_size read in xyz order
+    "half_away": dict(rounding="half_away"),   # round() of C instead of rint()
+    "unfused": dict(arith="unfused"),          # every product and sum rounded on its own, left to right
+    "floor_plus_1": dict(extent="floor_plus_1"),  # floor(x) + 1 in place of ceil(x)
+}
+VOXEL_MUTANTS = tuple(k for k in VOXELIZERS if k != "exact")
+
+
+def smpl_space_f32(verts, R, Th, arith="chain"):
+    """(v - Th) . R in float32, column by column, in the kernel's order -> [V,3] float32."""
+    from tests.cull_cases import dot3
+
+    verts, R, Th = np.asarray(verts, np.float32), np.asarray(R, np.float32), np.asarray(Th, np.float32).reshape(3)
+    d = [verts[:, k] - Th[k] for k in range(3)]
+    s = np.stack([dot3(d, R[:, i], arith) for i in range(3)], axis=1)
+    assert s.dtype == np.float32
+    return s
+
+
+def voxelize_f32(verts, R, Th, voxel_size, pad, variant="exact"):
+    """One frame: verts [V,3], R [3,3], Th [3] float32, voxel_size three Python floats (dhw), pad a key of PADS -> dict(coord [V,3]
+    i32 (dhw), bounds [2,3] f32 (SMPL space), out_sh [3] i32 (dhw), summary [9] i32) as restatement `variant` computes them."""
+    kw = VOXELIZERS[variant]
+    verts = np.asarray(verts, np.float32)
+    vs = np.array([float(v) for v in voxel_size], np.float64)
+    if kw.get("reverse_vs"):
+        vs = vs[::-1]
+    pd = np.array(PADS[pad], np.float32)
+    s = smpl_space_f32(verts, R, Th, kw.get("arith", "chain"))
+    wlo, whi = verts.min(axis=0) - pd, verts.max(axis=0) + pd
+    slo, shi = s.min(axis=0) - pd, s.max(axis=0) + pd
+    assert wlo.dtype == whi.dtype == slo.dtype == shi.dtype == np.float32
+    c = (s - slo[None])[:, ::-1].astype(np.float64) / vs[None]
+    coord = np.rint(c) if kw.get("rounding", "rint") == "rint" else np.trunc(c + np.copysign(0.5, c))
+    e = (shi - slo)[::-1].astype(np.float64) / vs
+    cells = np.ceil(e) if kw.get("extent", "ceil") == "ceil" else np.floor(e) + 1.0
+    out_sh = (cells.astype(np.int32) | 31) + 1
+    summary = np.concatenate([np.stack([wlo, whi]).reshape(-1).view(np.int32), out_sh])
+    return {"coord": coord.astype(np.int32), "bounds": np.stack([slo, shi]), "out_sh": out_sh, "summary": summary}

@@ -327,9 +327,15 @@ def test_full_training_step_gradients_match_autograd():
     """Renderer.render under autograd (encoder + decode + composite, forward and backward all HIP) against float64
     autograd through the whole oracle: the gradient of EVERY parameter (MLP, latent codes, 17 sparse conv weights,
     17 BatchNorm affine pairs, the 6890 vertex codes)."""
+    training_step_gradients_match_autograd()
+
+
+def training_step_gradients_match_autograd(voxel_size=None):
+    """The check of the test above; `voxel_size` (dhw, None: the fixtures' 5 mm cube) for tests/test_gpu_aniso_voxels.py."""
     from oracle import neuralbody_oracle as orc
 
-    r, sd, body, batch, cam, _ = scenes.build("small_dense")
+    r, sd, body, batch, cam, _ = scenes.build("small_dense", voxel_size)
+    vs = (0.005, 0.005, 0.005) if voxel_size is None else tuple(voxel_size)
     n_use = 96
     b_np = dict(batch)
     for k in ("ray_o", "ray_d", "near", "far"):
@@ -339,7 +345,7 @@ def test_full_training_step_gradients_match_autograd():
     # ---- HIP (first: its ReLU masks are handed to the reference)
     from neuralbody_amd import training
 
-    net = H.make_network(sd, DEV, True, "f32")
+    net = H.make_network(sd, DEV, True, "f32", voxel_size)
     rend = H.make_renderer(net, dict(r, white_bkgd=True))
     bd = H.device_batch(b_np, DEV)
     training.DEBUG_CAPTURE = {}
@@ -356,7 +362,7 @@ def test_full_training_step_gradients_match_autograd():
     for k, v in orc.tensor_state_dict(sd).items():
         sdg[k] = v.double().requires_grad_(True) if v.is_floating_point() and "running" not in k else v
     out_ref = orc.render(sdg, {k: (torch.from_numpy(v).double() if v.dtype == np.float32 else v) for k, v in b_np.items()},
-                         n_samples=64, training=True, white_bkgd=True, relu_masks=masks)
+                         n_samples=64, voxel_size=vs, training=True, white_bkgd=True, relu_masks=masks)
     (out_ref["rgb_map"] * g_rgb.double()).sum().backward()
     _rel(out["rgb_map"].detach().cpu().numpy(), out_ref["rgb_map"].detach().numpy(), 1e-4, "forward rgb")
     (out["rgb_map"] * g_rgb.to(DEV)).sum().backward()

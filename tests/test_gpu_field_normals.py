@@ -161,9 +161,15 @@ def test_chunks_agree():
 def test_gradient_against_float64_autograd_of_the_oracle(name):
     """On the oracle's own volumes (a plain list: the active set comes from nb_sparsify), at the 1024 samples of rays 0:256:16 less
     the points whose ReLU pattern or cell fp32 may decide the other way (computed from the reference alone, share under 10 %)."""
-    e = fc.e2e_reference(name)
+    gradient_against_float64_autograd(name)
+
+
+def gradient_against_float64_autograd(name, voxel_size=None, first_ray=0):
+    """The check of the test above; `voxel_size` (dhw, None: the fixtures' 5 mm cube) and `first_ray` for
+    tests/test_gpu_aniso_voxels.py."""
+    e = fc.e2e_reference(name, voxel_size, first_ray)
     assert 1.0 - e["keep"].mean() <= fc.EXCLUDE_CAP
-    net = H.make_network(e["sd"], DEV, e["recipe"]["mode"] == "train", "f32")
+    net = H.make_network(e["sd"], DEV, e["recipe"]["mode"] == "train", "f32", voxel_size)
     bd = H.device_batch(e["batch"], DEV)
     sp = H.sp_input_of(bd, e["out_sh"])
     with torch.no_grad():

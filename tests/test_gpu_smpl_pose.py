@@ -5,7 +5,10 @@ Vertices: max |device - float64 restatement| <= 4 x E_ref of the case (E_ref: th
 restatement, 1.4e-7 .. 2.7e-7 m in the fixture); device and reference are float32 evaluations of the same sums in another order.
 Voxelisation: `coord` is compared at every coordinate OUTSIDE the near band (smpl_ref.BAND: the float64 coordinate within 1e-3
 voxel of a half-integer), where a float32 evaluation may round to the other voxel whatever its order; inside it the difference is
-at most 1, and the band may not exceed 1 % of the coordinates."""
+at most 1, and the band may not exceed 1 % of the coordinates.  (tests/test_gpu_voxelize_exact.py holds the voxeliser to its
+operation-by-operation restatement at every coordinate, the band included.)
+Vertex blocks: V around the 64 vertices a workgroup skins, with guard frames behind every output; max |device - float64| <= 4 x E32,
+E32 the float32 restatement's largest error over the sweep (2.9e-7 m; measured 0.50 .. 0.77 x E32)."""
 import functools
 import os
 import types
@@ -164,6 +167,69 @@ def test_without_new_params_posedirs_is_never_read():
     b = PoseDriver(poisoned).vertices(*P, False)
     assert H.same_bits(a, b) and bool(torch.isfinite(b).all())
     assert bool(torch.isnan(PoseDriver(poisoned).vertices(*P, True)).all())  # and with them it is
+
+
+# ---------------------------------------------------------------------------------------------------------- 1b. vertex blocks
+SWEEP_V = (12, 63, 64, 65, 127, 129)  # nb_smpl_pose skins 64 vertices a workgroup; synthetic_smpl regresses a joint from 12
+SWEEP_FRAMES, GUARD_FRAMES, GUARD = 3, 2, -7.0
+
+
+@functools.lru_cache(maxsize=None)
+def _sweep():
+    """The sweep's models, parameters and float64 vertices, and E32: the largest error of the float32 restatement
+    sr.forward(dtype=np.float32) against the float64 one over the sweep's cases -- what 'the same float32 sums in another order'
+    costs here, computed on the host (1.0e-7 .. 2.7e-7 m a case, the size of the fixture's E_ref)."""
+    cases, e32 = {}, 0.0
+    for V in SWEEP_V:
+        m = sr.synthetic_smpl(300 + V, V, sr.SMPL_PARENTS)
+        P = [sr.draw_params(1300 + 10 * V + i) for i in range(SWEEP_FRAMES)]
+        for new_params in (False, True):
+            r64 = np.stack([sr.forward(m, *p, new_params, np.float64) for p in P])
+            e = max(float(np.abs(sr.forward(m, *p, new_params, np.float32).astype(np.float64) - r64[i]).max()) for i, p in enumerate(P))
+            e32 = max(e32, e)
+            r64.setflags(write=False)
+            cases[V, new_params] = dict(model=m, params=P, r64=r64, e32=e)
+    return cases, e32
+
+
+@functools.lru_cache(maxsize=None)
+def _sweep_model(V):
+    from neuralbody_amd.smpl_pose import SmplModel
+
+    return SmplModel.from_arrays(_sweep()[0][V, False]["model"], DEV)
+
+
+@pytest.mark.parametrize("new_params", [False, True])
+@pytest.mark.parametrize("V", SWEEP_V)
+def test_vertex_block_sweep_with_guard_rows(V, new_params):
+    """V around the 64-vertex block: three frames in one call against float64 (E_FACTOR x E32), behind them guard rows of verts,
+    joints and the workspace that the call must leave alone, and every frame again in a call of its own, bit for bit."""
+    from neuralbody_amd import _lib, ops
+    from neuralbody_amd.smpl_pose import pack_params
+
+    cases, e32 = _sweep()
+    c = cases[V, new_params]
+    native, _ = _sweep_model(V).native()
+    F, n = SWEEP_FRAMES, SWEEP_FRAMES + GUARD_FRAMES
+    params = pack_params(*[np.stack([p[k] for p in c["params"]]) for k in range(4)]).to(DEV)
+    verts = torch.full((n, V, 3), GUARD, device=DEV)
+    joints = torch.full((n, _lib.SMPL_JOINTS, 3), GUARD, device=DEV)
+    ws = torch.full((n, _lib.SMPL_WS_FLOATS), GUARD, device=DEV)
+    ops.smpl_pose(native, params, new_params, verts=verts[:F], joints=joints[:F], ws=ws[:F])
+    torch.cuda.synchronize()
+    for name, t in (("verts", verts), ("joints", joints), ("ws", ws)):
+        assert bool((t[F:] == GUARD).all()), "%s: written behind the %d frames" % (name, F)
+    got = verts[:F].cpu().numpy()
+    assert np.isfinite(got).all() and np.isfinite(joints[:F].cpu().numpy()).all()
+    err = float(np.abs(got.astype(np.float64) - c["r64"]).max())
+    print("V %d new_params %d: E32 %.3e (this case %.3e); max |device - fp64| %.3e = %.2f x E32" % (
+        V, new_params, e32, c["e32"], err, err / e32))
+    assert 5e-8 < e32 < 1e-6
+    assert err <= E_FACTOR * e32
+    for f in range(F):
+        alone, alone_j = ops.smpl_pose(native, params[f:f + 1].contiguous(), new_params)
+        assert H.same_bits(alone[0], verts[f]) and H.same_bits(alone_j[0], joints[f]), f
+    assert not H.same_bits(verts[0], verts[1])
 
 
 # ---------------------------------------------------------------------------------------------------------- 2. voxelisation
