@@ -181,27 +181,15 @@ struct RasterJob : Tri {
     const float *verts, *cams;
     const int *faces;
     int T, V, H, W;
-    unsigned long long *keys, *img;  // img, tri: the triangle's view and index, set by setup like the Tri
+    unsigned long long *out, *img;  // out: the keys [n_views, H, W]; img, tri: the triangle's view and index, set by setup like the Tri
     int tri;
     __device__ __forceinline__ bool setup(int g) {
         const int view = g / T;
-        tri = g - view * T, img = keys + (size_t)view * H * W;
+        tri = g - view * T, img = out + (size_t)view * H * W;
         return tri_setup(tri, faces, verts, V, cams + (size_t)view * CAM_FLOATS, H, W, *this);
     }
     __device__ __forceinline__ void pixel(int x, int y) { offer(*this, tri, x, y, img + (size_t)y * W); }
 };
-
-__global__ __launch_bounds__(256) void raster_small_kernel(RasterJob job, unsigned long long *__restrict__ keys, int n,
-                                                           int *__restrict__ count, int *__restrict__ large) {
-    job.keys = keys;  // a parameter for its __restrict__ (nb_raster.h)
-    nbraster::small_pass(job, n, count, large);
-}
-
-__global__ __launch_bounds__(256) void raster_large_kernel(RasterJob job, unsigned long long *__restrict__ keys, int n,
-                                                           const int *__restrict__ count, const int *__restrict__ large) {
-    job.keys = keys;  // a parameter for its __restrict__ (nb_raster.h)
-    nbraster::large_pass(job, n, count, large);
-}
 
 // One thread per pixel: the winner's sample again, by the functions that made the key, then its colour.  ATTR: `normals` holds the
 // vertex colours themselves (nb_mesh_render_attr) instead of the normals they are computed from.
@@ -292,9 +280,11 @@ int render(const char *what, const float *verts, const float *normals, const int
     NB_HIP(hipMemsetAsync(s.keys, 0xFF, 8 * (size_t)n_px, st));            // every key: nothing drawn
     if (n_tri > 0) {
         const RasterJob job = {{}, verts, cams, faces, T, V, H, W};
-        hipLaunchKernelGGL(raster_small_kernel, dim3(nb_ceil_div(n_tri, 256)), dim3(256), 0, st, job, s.keys, n_tri, s.hdr, s.large);
+        hipLaunchKernelGGL(nbraster::small_kernel<RasterJob>, dim3(nb_ceil_div(n_tri, 256)), dim3(256), 0, st, job, s.keys, n_tri, s.hdr,
+                           s.large);
         NB_CHECK_LAUNCH("nb_mesh_render (triangles)");
-        hipLaunchKernelGGL(raster_large_kernel, dim3(nbraster::LARGE_BLOCKS), dim3(256), 0, st, job, s.keys, n_tri, s.hdr, s.large);
+        hipLaunchKernelGGL(nbraster::large_kernel<RasterJob>, dim3(nbraster::LARGE_BLOCKS), dim3(256), 0, st, job, s.keys, n_tri, s.hdr,
+                           s.large);
         NB_CHECK_LAUNCH("nb_mesh_render (large triangles)");
     }
     hipLaunchKernelGGL(resolve_kernel<ATTR>, dim3(nb_ceil_div(n_px, 256)), dim3(256), 0, st, verts, normals, faces, cams, n_px, T, V, H, W,

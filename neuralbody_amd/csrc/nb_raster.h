@@ -1,4 +1,5 @@
-// Internal: the one triangle walker behind the silhouette rasteriser (nb_silhouette.hip) and the z-buffered one (nb_mesh_render.hip).
+// Internal: the one triangle walker, and its two kernels, behind the silhouette and depth-range rasterisers (nb_silhouette.hip) and the
+// z-buffered one (nb_mesh_render.hip).
 //
 // Triangles are binned by their clipped pixel box.  A box up to SMALL_BOX x SMALL_BOX is walked by the thread that set the triangle
 // up; the others go on a device-side list, which a fixed grid of LARGE_BLOCKS workgroups strides over, a workgroup per triangle.
@@ -8,8 +9,9 @@
 //     void pixel(int x, int y)    called once for every pixel of the box, by some thread, in no order
 // The large pass sets a listed triangle up again, so `setup` is a function of g alone.  The one atomic (a wave's slice of the list)
 // orders list entries, which no output bit depends on when `pixel` does not care about order.
-// A kernel takes the job by value but the pointer `pixel` writes through as a __restrict__ parameter of its own, stored into the
-// job (members cannot carry the qualifier; with the output among them both rasterisers measured 3 to 6 % slower).
+// The pointer `pixel` writes through is the job's member `out`.  small_kernel / large_kernel, which every rasteriser instantiates with
+// its job, take the job by value but that pointer as a __restrict__ parameter of their own, stored into the job before the pass
+// (members cannot carry the qualifier; with the output only a member both rasterisers measured 3 to 6 % slower).
 // Integer and control flow only: the callers round their floats in their own files, under their own contraction pragma.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -67,6 +69,21 @@ __device__ __forceinline__ void large_pass(Job &job, int n, const int *__restric
         const long long px = (long long)bw * (job.y1 - job.y0 + 1);
         for (long long p = threadIdx.x; p < px; p += 256) job.pixel(job.x0 + (int)(p % bw), job.y0 + (int)(p / bw));
     }
+}
+
+// The two launches of a rasteriser: small_kernel with a thread per triangle, then large_kernel with LARGE_BLOCKS workgroups.
+template <class Job>
+__global__ __launch_bounds__(256) void small_kernel(Job job, decltype(Job::out) __restrict__ out, int n, int *__restrict__ count,
+                                                    int *__restrict__ large) {
+    job.out = out;  // a parameter for its __restrict__ (above)
+    small_pass(job, n, count, large);
+}
+
+template <class Job>
+__global__ __launch_bounds__(256) void large_kernel(Job job, decltype(Job::out) __restrict__ out, int n, const int *__restrict__ count,
+                                                    const int *__restrict__ large) {
+    job.out = out;
+    large_pass(job, n, count, large);
 }
 
 }  // namespace nbraster

@@ -9,6 +9,8 @@
 // behind the snap is integer arithmetic (edge functions in int64, |coordinate| <= 2^23, every product < 2^48), so the mask is a
 // function of the inputs alone.  The output is a union of 1 bytes: racing identical stores, no ordering, the same bits every time.
 // The one atomic (a wave's slice of the large-triangle list) orders list entries, which no output bit depends on.
+// The two entries are one host function (raster<Job>) and one set of kernels: project_kernel<DEPTH>, a fill kernel each (they write
+// different types) and nb_raster.h's small_kernel / large_kernel with the entry's triangle job, SilJob or RangeJob.
 #include "nb_march_common.h"
 #include "nb_raster.h"
 
@@ -65,28 +67,19 @@ __device__ __forceinline__ bool project_snap(const float *__restrict__ verts, co
     return ok;
 }
 
-// One workgroup = 256 vertices of one (frame, view): the camera is wave-uniform.
-__global__ __launch_bounds__(256) void sil_project_kernel(const float *__restrict__ verts, const float *__restrict__ cam, int V, int nv,
-                                                          int chunks, int2 *__restrict__ snap, int *__restrict__ flags) {
-    const int fv = blockIdx.x / chunks, v = (blockIdx.x % chunks) * 256 + threadIdx.x;
-    if (v >= V) return;
-    int2 s;
-    float depth;
-    if (!project_snap(verts, cam, V, fv / nv, fv % nv, v, s, depth)) flags[fv] = 1;  // racing stores of the same value
-    snap[(size_t)fv * V + v] = s;
-}
-
-// the same, the vertex's camera depth kept beside its snapped coordinates
-__global__ __launch_bounds__(256) void range_project_kernel(const float *__restrict__ verts, const float *__restrict__ cam, int V, int nv,
-                                                            int chunks, int2 *__restrict__ snap, float *__restrict__ depth,
-                                                            int *__restrict__ flags) {
+// One workgroup = 256 vertices of one (frame, view): the camera is wave-uniform.  DEPTH: the vertex's camera depth is kept beside its
+// snapped coordinates (without it `depth` is not touched).
+template <bool DEPTH>
+__global__ __launch_bounds__(256) void project_kernel(const float *__restrict__ verts, const float *__restrict__ cam, int V, int nv,
+                                                      int chunks, int2 *__restrict__ snap, float *__restrict__ depth,
+                                                      int *__restrict__ flags) {
     const int fv = blockIdx.x / chunks, v = (blockIdx.x % chunks) * 256 + threadIdx.x;
     if (v >= V) return;
     int2 s;
     float z;
-    if (!project_snap(verts, cam, V, fv / nv, fv % nv, v, s, z)) flags[fv] = 1;
+    if (!project_snap(verts, cam, V, fv / nv, fv % nv, v, s, z)) flags[fv] = 1;  // racing stores of the same value
     snap[(size_t)fv * V + v] = s;
-    depth[(size_t)fv * V + v] = z;
+    if (DEPTH) depth[(size_t)fv * V + v] = z;
 }
 
 // range = (+inf, -inf) where the rasteriser will draw, (-inf, +inf) where the view does not bound.  A pixel per thread.
@@ -153,6 +146,7 @@ __device__ __forceinline__ bool tri_setup(int g, int Nf, int V, int H, int W, co
 
 // The triangle job of nb_raster.h: triangle g of the (frame, view, triangle) ids, a 1 byte wherever its pixel's square meets it.
 struct SilJob : Tri {
+    static constexpr bool DEPTH = false;
     const int *faces, *flags;
     const int2 *snap;
     int Nf, V, H, W;
@@ -162,22 +156,11 @@ struct SilJob : Tri {
     __device__ __forceinline__ void pixel(int x, int y) { if (covers(x, y)) out[((size_t)fv * H + y) * W + x] = 1; }
 };
 
-__global__ __launch_bounds__(256) void sil_small_kernel(SilJob job, unsigned char *__restrict__ out, int n, int *__restrict__ count,
-                                                        int *__restrict__ large) {
-    job.out = out;  // a parameter for its __restrict__ (nb_raster.h)
-    nbraster::small_pass(job, n, count, large);
-}
-
-__global__ __launch_bounds__(256) void sil_large_kernel(SilJob job, unsigned char *__restrict__ out, int n,
-                                                        const int *__restrict__ count, const int *__restrict__ large) {
-    job.out = out;  // a parameter for its __restrict__ (nb_raster.h)
-    nbraster::large_pass(job, n, count, large);
-}
-
 // The triangle job of nb_raster.h: triangle g of the (frame, view, triangle) ids, its vertex-depth interval folded into every pixel
 // whose square meets it.  Depths are >= MIN_DEPTH, so their fp32 bits order like signed integers, and so do the bits of the two
 // infinities the fill left: integer atomic min / max, the result free of the order of arrival.
 struct RangeJob : Tri {
+    static constexpr bool DEPTH = true;
     const int *faces, *flags;
     const int2 *snap;
     const float *depth;
@@ -202,16 +185,49 @@ struct RangeJob : Tri {
     }
 };
 
-__global__ __launch_bounds__(256) void range_small_kernel(RangeJob job, int *__restrict__ out, int n, int *__restrict__ count,
-                                                          int *__restrict__ large) {
-    job.out = out;  // a parameter for its __restrict__ (nb_raster.h)
-    nbraster::small_pass(job, n, count, large);
-}
-
-__global__ __launch_bounds__(256) void range_large_kernel(RangeJob job, int *__restrict__ out, int n, const int *__restrict__ count,
-                                                          const int *__restrict__ large) {
-    job.out = out;  // a parameter for its __restrict__ (nb_raster.h)
-    nbraster::large_pass(job, n, count, large);
+// Both entries: `what` names the caller in every message, the Job says which rasteriser runs.  DEPTH: the vertex depths are kept and
+// `out` is the fp32 range as its bits; the fills differ in what they write, and with it the grid-size refusal.
+template <class Job>
+int raster(const char *what, const float *verts, const int32_t *faces, const float *cam, int32_t F, int32_t V, int32_t Nf, int32_t nv,
+           int32_t H, int32_t W, void *scratch, int64_t scratch_bytes, decltype(Job::out) out, void *stream) {
+    constexpr bool DEPTH = Job::DEPTH;
+    NB_REQUIRE(verts && faces && cam && scratch && out, "%s: NULL pointer", what);
+    const Scratch s = carve(scratch, F, V, Nf, nv, DEPTH);
+    NB_REQUIRE(s.total_bytes > 0, "%s: F = %d (1..65535), V = %d, Nf = %d (>= 1), nv = %d (1..%d), F nv V and F nv Nf below 2^31 - 256",
+               what, F, V, Nf, nv, NB_MAX_CULL_VIEWS);
+    NB_REQUIRE(H >= 1 && W >= 1 && H <= 32768 && W <= 32768, "%s: H = %d, W = %d (1..32768)", what, H, W);
+    NB_REQUIRE(scratch_bytes >= s.total_bytes, "%s: scratch holds %lld bytes, %lld needed", what, (long long)scratch_bytes, s.total_bytes);
+    NB_REQUIRE(((uintptr_t)scratch & 15) == 0, "%s: scratch must be 16-byte aligned", what);
+    if constexpr (DEPTH) NB_REQUIRE(((uintptr_t)out & 7) == 0, "%s: range must be 8-byte aligned", what);
+    hipStream_t st = (hipStream_t)stream;
+    const int fv = F * nv, chunks = nb_ceil_div(V, 256), n_tri = fv * Nf;
+    const long long HW = (long long)H * W, n_px = HW * fv;
+    if constexpr (DEPTH)
+        NB_REQUIRE((n_px + 255) / 256 <= 2147483647ll, "%s: %lld pixels are too many", what, n_px);
+    else
+        NB_REQUIRE((n_px + 16 * 256 - 1) / (16 * 256) <= 2147483647ll, "%s: %lld output bytes are too many", what, n_px);
+    char where[64];  // "<what> (<step>)", written only when a launch failed
+    const auto at = [&](const char *step) { return snprintf(where, sizeof(where), "%s (%s)", what, step), where; };
+    int *flags = s.hdr + HDR_FLAGS, *count = s.hdr + HDR_COUNT;
+    NB_HIP(hipMemsetAsync(s.hdr, 0, (size_t)s.hdr_bytes, st));  // the count and every flag
+    hipLaunchKernelGGL(project_kernel<DEPTH>, dim3(fv * chunks), dim3(256), 0, st, verts, cam, V, nv, chunks, s.snap,
+                       DEPTH ? s.depth : nullptr, flags);
+    NB_CHECK_LAUNCH(at("project"));
+    Job job = {};
+    job.faces = faces, job.flags = flags, job.snap = s.snap, job.Nf = Nf, job.V = V, job.H = H, job.W = W;
+    if constexpr (DEPTH) {
+        job.depth = s.depth;
+        hipLaunchKernelGGL(range_fill_kernel, dim3(nb_ceil_div(n_px, 256)), dim3(256), 0, st, flags, HW, n_px, (float2 *)out);
+    } else {
+        hipLaunchKernelGGL(sil_fill_kernel, dim3(nb_ceil_div(n_px, 16 * 256)), dim3(256), 0, st, flags, HW, n_px,
+                           ((uintptr_t)out & 15) == 0 ? 1 : 0, out);
+    }
+    NB_CHECK_LAUNCH(at("fill"));
+    hipLaunchKernelGGL(nbraster::small_kernel<Job>, dim3(nb_ceil_div(n_tri, 256)), dim3(256), 0, st, job, out, n_tri, count, s.large);
+    NB_CHECK_LAUNCH(at("triangles"));
+    hipLaunchKernelGGL(nbraster::large_kernel<Job>, dim3(nbraster::LARGE_BLOCKS), dim3(256), 0, st, job, out, n_tri, count, s.large);
+    NB_CHECK_LAUNCH(at("large triangles"));
+    return NB_OK;
 }
 
 }  // namespace
@@ -223,32 +239,7 @@ extern "C" int64_t nb_smpl_silhouette_scratch_size(int32_t F, int32_t V, int32_t
 extern "C" int nb_smpl_silhouette(const float *verts, const int32_t *faces, const float *cam, int32_t F, int32_t V, int32_t Nf,
                                   int32_t nv, int32_t H, int32_t W, void *scratch, int64_t scratch_bytes, uint8_t *out,
                                   void *stream) {
-    NB_REQUIRE(verts && faces && cam && scratch && out, "nb_smpl_silhouette: NULL pointer");
-    const Scratch s = carve(scratch, F, V, Nf, nv);
-    NB_REQUIRE(s.total_bytes > 0,
-               "nb_smpl_silhouette: F = %d (1..65535), V = %d, Nf = %d (>= 1), nv = %d (1..%d), F nv V and F nv Nf below 2^31 - 256", F, V,
-               Nf, nv, NB_MAX_CULL_VIEWS);
-    NB_REQUIRE(H >= 1 && W >= 1 && H <= 32768 && W <= 32768, "nb_smpl_silhouette: H = %d, W = %d (1..32768)", H, W);
-    NB_REQUIRE(scratch_bytes >= s.total_bytes, "nb_smpl_silhouette: scratch holds %lld bytes, %lld needed", (long long)scratch_bytes,
-               s.total_bytes);
-    NB_REQUIRE(((uintptr_t)scratch & 15) == 0, "nb_smpl_silhouette: scratch must be 16-byte aligned");
-    hipStream_t st = (hipStream_t)stream;
-    const int fv = F * nv, chunks = nb_ceil_div(V, 256), n_tri = fv * Nf;
-    const long long HW = (long long)H * W, n_px = HW * fv;
-    NB_REQUIRE((n_px + 16 * 256 - 1) / (16 * 256) <= 2147483647ll, "nb_smpl_silhouette: %lld output bytes are too many", n_px);
-    int *flags = s.hdr + HDR_FLAGS, *count = s.hdr + HDR_COUNT;
-    NB_HIP(hipMemsetAsync(s.hdr, 0, (size_t)s.hdr_bytes, st));  // the count and every flag
-    hipLaunchKernelGGL(sil_project_kernel, dim3(fv * chunks), dim3(256), 0, st, verts, cam, V, nv, chunks, s.snap, flags);
-    NB_CHECK_LAUNCH("nb_smpl_silhouette (project)");
-    hipLaunchKernelGGL(sil_fill_kernel, dim3(nb_ceil_div(n_px, 16 * 256)), dim3(256), 0, st, flags, HW, n_px,
-                       ((uintptr_t)out & 15) == 0 ? 1 : 0, out);
-    NB_CHECK_LAUNCH("nb_smpl_silhouette (fill)");
-    const SilJob job = {{}, faces, flags, s.snap, Nf, V, H, W};
-    hipLaunchKernelGGL(sil_small_kernel, dim3(nb_ceil_div(n_tri, 256)), dim3(256), 0, st, job, out, n_tri, count, s.large);
-    NB_CHECK_LAUNCH("nb_smpl_silhouette (triangles)");
-    hipLaunchKernelGGL(sil_large_kernel, dim3(nbraster::LARGE_BLOCKS), dim3(256), 0, st, job, out, n_tri, count, s.large);
-    NB_CHECK_LAUNCH("nb_smpl_silhouette (large triangles)");
-    return NB_OK;
+    return raster<SilJob>("nb_smpl_silhouette", verts, faces, cam, F, V, Nf, nv, H, W, scratch, scratch_bytes, out, stream);
 }
 
 extern "C" int64_t nb_body_depth_range_scratch_size(int32_t F, int32_t V, int32_t Nf, int32_t nv) {
@@ -257,30 +248,5 @@ extern "C" int64_t nb_body_depth_range_scratch_size(int32_t F, int32_t V, int32_
 
 extern "C" int nb_body_depth_range(const float *verts, const int32_t *faces, const float *cam, int32_t F, int32_t V, int32_t Nf,
                                    int32_t nv, int32_t H, int32_t W, void *scratch, int64_t scratch_bytes, float *range, void *stream) {
-    NB_REQUIRE(verts && faces && cam && scratch && range, "nb_body_depth_range: NULL pointer");
-    const Scratch s = carve(scratch, F, V, Nf, nv, true);
-    NB_REQUIRE(s.total_bytes > 0,
-               "nb_body_depth_range: F = %d (1..65535), V = %d, Nf = %d (>= 1), nv = %d (1..%d), F nv V and F nv Nf below 2^31 - 256", F, V,
-               Nf, nv, NB_MAX_CULL_VIEWS);
-    NB_REQUIRE(H >= 1 && W >= 1 && H <= 32768 && W <= 32768, "nb_body_depth_range: H = %d, W = %d (1..32768)", H, W);
-    NB_REQUIRE(scratch_bytes >= s.total_bytes, "nb_body_depth_range: scratch holds %lld bytes, %lld needed", (long long)scratch_bytes,
-               s.total_bytes);
-    NB_REQUIRE(((uintptr_t)scratch & 15) == 0, "nb_body_depth_range: scratch must be 16-byte aligned");
-    NB_REQUIRE(((uintptr_t)range & 7) == 0, "nb_body_depth_range: range must be 8-byte aligned");
-    hipStream_t st = (hipStream_t)stream;
-    const int fv = F * nv, chunks = nb_ceil_div(V, 256), n_tri = fv * Nf;
-    const long long HW = (long long)H * W, n_px = HW * fv;
-    NB_REQUIRE((n_px + 255) / 256 <= 2147483647ll, "nb_body_depth_range: %lld pixels are too many", n_px);
-    int *flags = s.hdr + HDR_FLAGS, *count = s.hdr + HDR_COUNT;
-    NB_HIP(hipMemsetAsync(s.hdr, 0, (size_t)s.hdr_bytes, st));  // the count and every flag
-    hipLaunchKernelGGL(range_project_kernel, dim3(fv * chunks), dim3(256), 0, st, verts, cam, V, nv, chunks, s.snap, s.depth, flags);
-    NB_CHECK_LAUNCH("nb_body_depth_range (project)");
-    hipLaunchKernelGGL(range_fill_kernel, dim3(nb_ceil_div(n_px, 256)), dim3(256), 0, st, flags, HW, n_px, (float2 *)range);
-    NB_CHECK_LAUNCH("nb_body_depth_range (fill)");
-    const RangeJob job = {{}, faces, flags, s.snap, s.depth, Nf, V, H, W};
-    hipLaunchKernelGGL(range_small_kernel, dim3(nb_ceil_div(n_tri, 256)), dim3(256), 0, st, job, (int *)range, n_tri, count, s.large);
-    NB_CHECK_LAUNCH("nb_body_depth_range (triangles)");
-    hipLaunchKernelGGL(range_large_kernel, dim3(nbraster::LARGE_BLOCKS), dim3(256), 0, st, job, (int *)range, n_tri, count, s.large);
-    NB_CHECK_LAUNCH("nb_body_depth_range (large triangles)");
-    return NB_OK;
+    return raster<RangeJob>("nb_body_depth_range", verts, faces, cam, F, V, Nf, nv, H, W, scratch, scratch_bytes, (int *)range, stream);
 }

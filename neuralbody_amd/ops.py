@@ -559,29 +559,37 @@ def enc_gather_codes(codes, rows_vert, n_rows, n_rows_max):
 
 
 # --------------------------------------------------------------------------------- ray generation
-def raygen(H, W, K, R, T, bounds, device):
-    """nb_raygen: K, R [3,3], T [3] host float64 arrays; bounds [2,3] host float32 (world AABB).
-    Returns device tensors (ray_o, ray_d, near, far, mask_at_box, n_rays[1]) with H*W capacity; the
-    first n_rays rows are valid."""
+def _host_cam(K, R, T, bounds):
+    """The host camera block of the ray entries: K, R [3,3], T [3] as C doubles and bounds [2,3] as C floats."""
     import numpy as np
 
     K = np.asarray(K, np.float64).reshape(9)
     R = np.asarray(R, np.float64).reshape(9)
     T = np.asarray(T, np.float64).reshape(3)
     b = np.asarray(bounds, np.float32).reshape(6)
-    n = int(H) * int(W)
+    return (C.c_double * 9)(*K), (C.c_double * 9)(*R), (C.c_double * 3)(*T), (C.c_float * 6)(*b)
+
+
+def _raygen_buffers(n, device):
+    """raygen's 6-tuple for n pixels (ray_o, ray_d, near, far, mask_at_box, n_rays[1]) and the scan scratch."""
     ray_o = torch.empty((n, 3), dtype=torch.float32, device=device)
     ray_d = torch.empty((n, 3), dtype=torch.float32, device=device)
     near = torch.empty(n, dtype=torch.float32, device=device)
     far = torch.empty(n, dtype=torch.float32, device=device)
     mask = torch.empty(n, dtype=torch.uint8, device=device)
     n_rays = torch.zeros(1, dtype=torch.int32, device=device)
-    scratch = scan_scratch(n, device)
+    return (ray_o, ray_d, near, far, mask, n_rays), scan_scratch(n, device)
+
+
+def raygen(H, W, K, R, T, bounds, device):
+    """nb_raygen: K, R [3,3], T [3] host float64 arrays; bounds [2,3] host float32 (world AABB).
+    Returns device tensors (ray_o, ray_d, near, far, mask_at_box, n_rays[1]) with H*W capacity; the
+    first n_rays rows are valid."""
+    cam = _host_cam(K, R, T, bounds)
+    out, scratch = _raygen_buffers(int(H) * int(W), device)
     with torch.cuda.device(device):
-        check(_lib.lib().nb_raygen(int(H), int(W), (C.c_double * 9)(*K), (C.c_double * 9)(*R), (C.c_double * 3)(*T),
-                                   (C.c_float * 6)(*b), ptr(ray_o), ptr(ray_d), ptr(near), ptr(far), ptr(mask),
-                                   ptr(n_rays), ptr(scratch), _stream()), "nb_raygen")
-    return ray_o, ray_d, near, far, mask, n_rays
+        check(_lib.lib().nb_raygen(int(H), int(W), *cam, *(ptr(t) for t in out), ptr(scratch), _stream()), "nb_raygen")
+    return out
 
 
 def train_rays_scratch(H, W, device):
@@ -610,10 +618,7 @@ def train_rays(img, msk, K, R, T, bounds, hull, mode, body_ratio, u, scratch=Non
     if msk.device != dev or u.device != dev:
         raise ValueError("img, msk and u must share one device")
     n_rounds, n = int(u.shape[0]), int(u.shape[1])
-    K = np.asarray(K, np.float64).reshape(9)
-    R = np.asarray(R, np.float64).reshape(9)
-    T = np.asarray(T, np.float64).reshape(3)
-    b = np.asarray(bounds, np.float32).reshape(6)
+    cam = _host_cam(K, R, T, bounds)
     hull = np.ascontiguousarray(np.asarray(hull, np.int64).reshape(-1, 2))
     if np.abs(hull).max(initial=0) >= 1 << 30:
         raise ValueError("train_rays: hull coordinate with magnitude >= 2^30")
@@ -625,8 +630,7 @@ def train_rays(img, msk, K, R, T, bounds, hull, mode, body_ratio, u, scratch=Non
            "far": torch.empty(n, dtype=torch.float32, device=dev), "pixel": torch.empty((n, 2), dtype=torch.int32, device=dev),
            "mask_at_box": torch.empty(n, dtype=torch.uint8, device=dev), "status": torch.empty(4, dtype=torch.int32, device=dev)}
     with torch.cuda.device(dev):
-        check(_lib.lib().nb_train_rays(H, W, (C.c_double * 9)(*K), (C.c_double * 9)(*R), (C.c_double * 3)(*T), (C.c_float * 6)(*b),
-                                       C.cast(hull_c, C.c_void_p), hull.shape[0], ptr(msk), ptr(img), _lib.SAMPLE_MODES[mode],
+        check(_lib.lib().nb_train_rays(H, W, *cam, C.cast(hull_c, C.c_void_p), hull.shape[0], ptr(msk), ptr(img), _lib.SAMPLE_MODES[mode],
                                        float(body_ratio), ptr(u), n_rounds, n, ptr(out["rgb"]), ptr(out["ray_o"]),
                                        ptr(out["ray_d"]), ptr(out["near"]), ptr(out["far"]), ptr(out["pixel"]),
                                        ptr(out["mask_at_box"]), ptr(out["status"]), ptr(scratch), _stream()), "nb_train_rays")
@@ -1418,10 +1422,8 @@ def smpl_silhouette_scratch(F, V, Nf, nv, device):
                            "nv = %d (F 1..65535, nv 1..64, F nv V and F nv Nf < 2^31)")
 
 
-def smpl_silhouette(verts, faces, RT, K, H, W, out=None, scratch=None):
-    """nb_smpl_silhouette: verts device fp32 [F,V,3] (world), faces device int32 [Nf,3] (indices 0..V-1, validated where the list
-    is made: SmplModel), RT [nv,3,4], K [nv,3,3] device tensors (the cull cameras, as make_cull takes them), H, W the mask size
-    -> device uint8 [F,nv,H,W], 1 where the body's triangles meet the pixel; nothing is read back."""
+def _body_raster(entry, scratch_fn, out_dtype, out_tail, verts, faces, RT, K, H, W, out, scratch):
+    """smpl_silhouette and body_depth_range: the posed body's triangles through the cull cameras into `out`, [F,nv,H,W] + out_tail."""
     _req(verts, torch.float32, (None, None, 3), "verts")
     _req(faces, torch.int32, (None, 3), "faces")
     F, V, Nf, dev = int(verts.shape[0]), int(verts.shape[1]), int(faces.shape[0]), verts.device
@@ -1438,15 +1440,22 @@ def smpl_silhouette(verts, faces, RT, K, H, W, out=None, scratch=None):
         raise ValueError("verts, faces, RT and K live on different devices")
     cam = _cull_cams(RT, K, nv)
     if scratch is None:
-        scratch = smpl_silhouette_scratch(F, V, Nf, nv, dev)
+        scratch = scratch_fn(F, V, Nf, nv, dev)
     _req(scratch, torch.uint8, (None,), "scratch")
     if out is None:
-        out = torch.empty((F, nv, H, W), dtype=torch.uint8, device=dev)
-    _req(out, torch.uint8, (F, nv, H, W), "out")
+        out = torch.empty((F, nv, H, W) + out_tail, dtype=out_dtype, device=dev)
+    _req(out, out_dtype, (F, nv, H, W) + out_tail, "out")
     with torch.cuda.device(dev):
-        check(_lib.lib().nb_smpl_silhouette(ptr(verts), ptr(faces), ptr(cam), F, V, Nf, nv, H, W, ptr(scratch), int(scratch.numel()),
-                                            ptr(out), _stream()), "nb_smpl_silhouette")
+        check(getattr(_lib.lib(), entry)(ptr(verts), ptr(faces), ptr(cam), F, V, Nf, nv, H, W, ptr(scratch), int(scratch.numel()),
+                                         ptr(out), _stream()), entry)
     return out
+
+
+def smpl_silhouette(verts, faces, RT, K, H, W, out=None, scratch=None):
+    """nb_smpl_silhouette: verts device fp32 [F,V,3] (world), faces device int32 [Nf,3] (indices 0..V-1, validated where the list
+    is made: SmplModel), RT [nv,3,4], K [nv,3,3] device tensors (the cull cameras, as make_cull takes them), H, W the mask size
+    -> device uint8 [F,nv,H,W], 1 where the body's triangles meet the pixel; nothing is read back."""
+    return _body_raster("nb_smpl_silhouette", smpl_silhouette_scratch, torch.uint8, (), verts, faces, RT, K, H, W, out, scratch)
 
 
 # ------------------------------------------------------------------------------------------- ray bounds from the posed body
@@ -1460,31 +1469,7 @@ def body_depth_range(verts, faces, RT, K, H, W, out=None, scratch=None):
     """nb_body_depth_range: the arguments of smpl_silhouette -> device fp32 [F,nv,H,W,2], per pixel the smallest and the largest
     camera depth of the vertices of the triangles that meet it: (+inf, -inf) where none does, (-inf, +inf) all over a view that does
     not bound (a vertex nearer than 0.01 m or projecting beyond 32768 px); nothing is read back."""
-    _req(verts, torch.float32, (None, None, 3), "verts")
-    _req(faces, torch.int32, (None, 3), "faces")
-    F, V, Nf, dev = int(verts.shape[0]), int(verts.shape[1]), int(faces.shape[0]), verts.device
-    H, W = int(H), int(W)
-    if F < 1 or V < 1 or Nf < 1:
-        raise ValueError("verts %s or faces %s is empty" % (tuple(verts.shape), tuple(faces.shape)))
-    if not 1 <= H <= 32768 or not 1 <= W <= 32768:
-        raise ValueError("H = %d, W = %d (1..32768)" % (H, W))
-    _on_device(RT, "RT")
-    nv = int(_on_device(K, "K").shape[0])
-    if tuple(RT.shape) != (nv, 3, 4) or tuple(K.shape) != (nv, 3, 3):
-        raise ValueError("RT %s, K %s: expected [%d,3,4] and [%d,3,3]" % (tuple(RT.shape), tuple(K.shape), nv, nv))
-    if faces.device != dev or RT.device != dev or K.device != dev:
-        raise ValueError("verts, faces, RT and K live on different devices")
-    cam = _cull_cams(RT, K, nv)
-    if scratch is None:
-        scratch = body_depth_range_scratch(F, V, Nf, nv, dev)
-    _req(scratch, torch.uint8, (None,), "scratch")
-    if out is None:
-        out = torch.empty((F, nv, H, W, 2), dtype=torch.float32, device=dev)
-    _req(out, torch.float32, (F, nv, H, W, 2), "out")
-    with torch.cuda.device(dev):
-        check(_lib.lib().nb_body_depth_range(ptr(verts), ptr(faces), ptr(cam), F, V, Nf, nv, H, W, ptr(scratch), int(scratch.numel()),
-                                             ptr(out), _stream()), "nb_body_depth_range")
-    return out
+    return _body_raster("nb_body_depth_range", body_depth_range_scratch, torch.float32, (2,), verts, faces, RT, K, H, W, out, scratch)
 
 
 def depth_range_widen(ranges, border=1, tile=1, out=None):
@@ -1515,28 +1500,15 @@ def raygen_body(H, W, K, R, T, bounds, depth_range, margin=0.0):
     """nb_raygen_body: raygen's host arguments, depth_range device fp32 [H,W,2] (body_depth_range of the SAME camera, widened) and
     margin in metres: near = max(near, range0 - margin), far = min(far, range1 + margin), a pixel kept iff raygen keeps it and
     near < far.  K's last row must be (0, 0, 1).  Returns raygen's 6-tuple on depth_range's device."""
-    import numpy as np
-
     H, W = int(H), int(W)
     _req(depth_range, torch.float32, (H, W, 2), "depth_range")
     device = depth_range.device
-    K = np.asarray(K, np.float64).reshape(9)
-    R = np.asarray(R, np.float64).reshape(9)
-    T = np.asarray(T, np.float64).reshape(3)
-    b = np.asarray(bounds, np.float32).reshape(6)
-    n = H * W
-    ray_o = torch.empty((n, 3), dtype=torch.float32, device=device)
-    ray_d = torch.empty((n, 3), dtype=torch.float32, device=device)
-    near = torch.empty(n, dtype=torch.float32, device=device)
-    far = torch.empty(n, dtype=torch.float32, device=device)
-    mask = torch.empty(n, dtype=torch.uint8, device=device)
-    n_rays = torch.zeros(1, dtype=torch.int32, device=device)
-    scratch = scan_scratch(n, device)
+    cam = _host_cam(K, R, T, bounds)
+    out, scratch = _raygen_buffers(H * W, device)
     with torch.cuda.device(device):
-        check(_lib.lib().nb_raygen_body(H, W, (C.c_double * 9)(*K), (C.c_double * 9)(*R), (C.c_double * 3)(*T), (C.c_float * 6)(*b),
-                                        ptr(depth_range), float(margin), ptr(ray_o), ptr(ray_d), ptr(near), ptr(far), ptr(mask),
-                                        ptr(n_rays), ptr(scratch), _stream()), "nb_raygen_body")
-    return ray_o, ray_d, near, far, mask, n_rays
+        check(_lib.lib().nb_raygen_body(H, W, *cam, ptr(depth_range), float(margin), *(ptr(t) for t in out), ptr(scratch), _stream()),
+              "nb_raygen_body")
+    return out
 
 
 # ------------------------------------------------------------------------------------------- pictures of an extracted mesh

@@ -1,5 +1,5 @@
-"""Numpy restatement of the ray bounds (csrc/nb_silhouette.hip: nb_body_depth_range; csrc/nb_ray_bounds.hip: nb_depth_range_widen,
-nb_raygen_body), include/nb_hip.h's definitions evaluated on the host, and the cases their suites share.  CPU only.
+"""Numpy restatement of the ray bounds (csrc/nb_silhouette.hip: nb_body_depth_range; csrc/nb_ray_bounds.hip: nb_depth_range_widen;
+csrc/nb_raygen.hip: nb_raygen_body), include/nb_hip.h's definitions evaluated on the host, and the cases their suites share.  CPU only.
 
     depth_range   silhouette_ref.snapped_mask's loop, every triangle carrying the min / max of its three vertices' fp32 camera depths
                   (R v + T).z in the `chain` arithmetic of tests/cull_cases.py, the value the projection computes
