@@ -1015,6 +1015,51 @@ int nb_raygen_body(int32_t H, int32_t W, const double K[9], const double R[9], c
                    const float *range, float margin, float *ray_o, float *ray_d, float *near, float *far, uint8_t *mask_at_box,
                    int32_t *n_rays, void *scratch, void *stream);
 
+/* ---------------------------------------------------------------------------------
+ * The vanilla-NeRF baseline (configs/nerf/nerf_313.yaml: lib/networks/nerf.py and lib/networks/renderer/volume_renderer.py), inference
+ * only: the 8 x 256 coordinate MLP with its skip connection and view branch as one kernel, and the depth-only merge its fine pass
+ * needs.  The supported network is the one the reference ships: D = 8, W = 256, skips = [4], use_viewdirs, xyz_res 10, view_res 4.
+ * No allocation, no synchronisation, everything on `stream`, no atomics: the same inputs give the same bits.
+ * nb_nerf_params — HOST struct of DEVICE pointers to one Nerf module's parameters in the reference's shapes (nerf.py:27-43), fp32,
+ *   row-major [out, in]: pts_w[0] [256,63], pts_w[1..4,6,7] [256,256], pts_w[5] [256,319] (columns [input_pts 63, h 256], nerf.py:53),
+ *   pts_b[i] [256]; views_w [128,283] (columns [feature 256, input_views 27], nerf.py:58), views_b [128]; feature_w [256,256],
+ *   feature_b [256]; alpha_w [1,256], alpha_b [1]; rgb_w [3,128], rgb_b [3].
+ * nb_nerf_pack_size(precision) — floats of the packed blob (the same for both precisions; 0 for any other).
+ * nb_nerf_pack — writes the blob once: the ten matrices in MFMA fragment order with the skip and view layers' columns permuted to
+ *   the kernel's row order and K padded with zeros to a multiple of 16, then the biases and the two heads.  packed dev, 16-byte
+ *   aligned.  Eleven launches.
+ * nb_nerf_decode — raw [n_rays, n_samples, 4] (rgb before the sigmoid, sigma before the relu: nerf.py:65) at the depths z_vals
+ *   [n_rays, n_samples] of the rays ray_o, ray_d [n_rays, 3].  Per sample, in this order:
+ *     p = fl32(o + fl32(d * z)) per axis; v = d / |d| formed in float64 and rounded once (nb_importance_sample's definitions);
+ *     the embeddings [x, sin(2^k x), cos(2^k x)]_k (embedder.py:26-36), k < 10 for p and k < 4 for v: x / (2 pi) in float64,
+ *       scaled exactly, its fractional revolution to the hardware sine (<= 4e-7 absolute against torch.sin / cos of the fp32 argument);
+ *     h = relu(pts_linears[i](h)), i = 0..7, with h = [embed(p), h] before layer 5; alpha = alpha_linear(h); feature = feature_linear(h);
+ *     rgb = rgb_linear(relu(views_linears[0]([feature, embed(v)]))); raw = [rgb, alpha].
+ *   NB_PREC_F32: every product an fp32 fma into an fp32 accumulator that starts at the bias (v_mfma_f32_32x32x2_f32 for the ten
+ *   matrices); the summation order is written out at the top of csrc/nb_nerf.hip.  NB_PREC_F16X3 (nb_nerf_* only): the ten matrices
+ *   on v_mfma_f32_32x32x16_f16 with fp32 accumulation, weights and activations split into an fp16 head and an fp16 remainder, three
+ *   products (head.head + head.remainder + remainder.head); biases and the two heads of the network stay fp32.  fp16's range: an
+ *   activation above 65504 becomes inf.  A blob serves the precision it was packed for.  Any other precision is NB_EINVAL.
+ *   One workgroup carries 64 samples through all layers in LDS; n_rays * n_samples need not be a multiple of 64.
+ *   Sizes, else NB_EINVAL: 0 <= n_rays < 2^31 (n_rays == 0: NB_OK at once), 1 <= n_samples <= 512.  NULL pointers, a packed that is
+ *   not 16-byte aligned or another pointer that is not 4-byte aligned: NB_EINVAL with a message.  One launch.
+ * nb_importance_merge_z — torch.sort(torch.cat([z_vals, z_samples], -1), -1) (volume_renderer.py:93) for depths alone, as the
+ *   baseline's fine pass re-evaluates every merged depth: nb_importance_merge's counting rule (one device function ranks for
+ *   both) and sizes, without any raw.  z_coarse [n_rays, n_samples], z_fine [n_rays, n_importance] -> z_vals [n_rays, n_samples +
+ *   n_importance].
+ * ------------------------------------------------------------------------------- */
+#define NB_PREC_F16X3 2 /* nb_nerf_pack / nb_nerf_decode only: fp16 head + remainder, three products, fp32 accumulate */
+typedef struct nb_nerf_params {
+    const float *pts_w[8], *pts_b[8];
+    const float *views_w, *views_b, *feature_w, *feature_b, *alpha_w, *alpha_b, *rgb_w, *rgb_b;
+} nb_nerf_params;
+int64_t nb_nerf_pack_size(int precision);
+int nb_nerf_pack(const nb_nerf_params *params, float *packed, int precision, void *stream);
+int nb_nerf_decode(const float *packed, const float *ray_o, const float *ray_d, const float *z_vals, int64_t n_rays,
+                   int32_t n_samples, float *raw, int precision, void *stream);
+int nb_importance_merge_z(const float *z_coarse, const float *z_fine, int64_t n_rays, int32_t n_samples, int32_t n_importance,
+                          float *z_vals, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -76,6 +76,11 @@ class NbMlpParams(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in MLP_PARAM_FIELDS]
 
 
+class NbNerfParams(C.Structure):  # nb_nerf_params: one Nerf module's parameters (device pointers)
+    _fields_ = [("pts_w", C.c_void_p * 8), ("pts_b", C.c_void_p * 8)] + \
+               [(n, C.c_void_p) for n in ("views_w", "views_b", "feature_w", "feature_b", "alpha_w", "alpha_b", "rgb_w", "rgb_b")]
+
+
 _P = C.c_void_p
 _I32 = C.c_int32
 _I64 = C.c_int64
@@ -169,6 +174,10 @@ SIGNATURES = {
     "nb_depth_range_widen": (C.c_int, [_P, _I32, _I32, _I32, _I32, _I32, _P, _P]),
     "nb_raygen_body": (C.c_int, [_I32, _I32, C.c_double * 9, C.c_double * 9, C.c_double * 3, C.c_float * 6, _P, C.c_float, _P, _P,
                                  _P, _P, _P, _P, _P, _P]),
+    "nb_nerf_pack_size": (_I64, [C.c_int]),
+    "nb_nerf_pack": (C.c_int, [C.POINTER(NbNerfParams), _P, C.c_int, _P]),
+    "nb_nerf_decode": (C.c_int, [_P, _P, _P, _P, _I64, _I32, _P, C.c_int, _P]),
+    "nb_importance_merge_z": (C.c_int, [_P, _P, _I64, _I32, _I32, _P, _P]),
 }
 
 _lib = None

@@ -1,5 +1,5 @@
 // nb_importance.hip — hierarchical sampling behind the march: the importance depths of every ray (nb_importance_sample) and the
-// stable merge of the coarse and the fine samples of a ray by depth (nb_importance_merge).  The decode of the new points is
+// stable merge of the coarse and the fine samples of a ray by depth (nb_importance_merge; nb_importance_merge_z for depths alone).  The decode of the new points is
 // nb_decode_points, the second quadrature nb_composite: this file is the per-ray work between them.
 //
 // Restates (zju3dv/neuralbody):
@@ -26,6 +26,7 @@
 // Everything else is one IEEE operation per line (no contraction).  z_std is formed in float64 from the fp32 depths and rounded once.
 // No atomics: the same inputs give the same bits.
 #include "nb_march_common.h"
+#include "nb_merge_rank.h"
 
 namespace {
 
@@ -144,8 +145,7 @@ __global__ __launch_bounds__(256) void importance_sample_kernel(SampleArgs a) {
     if (live && lane == 0) a.z_std[ray] = (float)sqrt(dsq / (double)N);
 }
 
-// Rank by counting: entry e of the concatenation (coarse 0..S-1, then fine) goes to the slot whose number is the count of entries
-// with a smaller depth plus the earlier entries with the same depth — a stable sort, whatever order the inputs come in.
+// (merge_load, merge_rank: nb_merge_rank.h, shared by the two merge kernels)
 __global__ __launch_bounds__(256) void importance_merge_kernel(const float *__restrict__ z_coarse, const float *__restrict__ raw_coarse,
                                                                const float *__restrict__ z_fine, const float *__restrict__ raw_fine,
                                                                const unsigned char *__restrict__ keep, long long n_rays, int S, int N,
@@ -157,16 +157,12 @@ __global__ __launch_bounds__(256) void importance_merge_kernel(const float *__re
     const long long ray = live ? ray_raw : n_rays - 1;
     const int T = S + N;
     float *z = s_z[wv];
-    for (int e = lane; e < T; e += 64) z[e] = e < S ? z_coarse[ray * S + e] : z_fine[ray * N + (e - S)];
+    merge_load(z, z_coarse, z_fine, ray, S, N, lane);
     __syncthreads();
     if (!live) return;
     for (int e = lane; e < T; e += 64) {
         const float ze = z[e];
-        int rank = 0;
-        for (int j = 0; j < T; ++j) {  // (every lane reads the same word: an LDS broadcast)
-            const float zj = z[j];
-            rank += (zj < ze || (zj == ze && j < e)) ? 1 : 0;
-        }
+        const int rank = merge_rank(z, T, e);
         f32x4 r;
         if (e < S) {
             r = *reinterpret_cast<const f32x4 *>(raw_coarse + (ray * S + e) * 4);
@@ -180,7 +176,23 @@ __global__ __launch_bounds__(256) void importance_merge_kernel(const float *__re
     }
 }
 
-// the sizes both entries accept
+// nb_importance_merge without the raw: the depths alone (volume_renderer.py:93 as the baseline's fine pass uses it)
+__global__ __launch_bounds__(256) void importance_merge_z_kernel(const float *__restrict__ z_coarse, const float *__restrict__ z_fine,
+                                                                 long long n_rays, int S, int N, float *__restrict__ z_out) {
+    __shared__ float s_z[RAYS_PER_BLOCK][MERGED_MAX];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const long long ray_raw = (long long)blockIdx.x * RAYS_PER_BLOCK + wv;
+    const bool live = ray_raw < n_rays;
+    const long long ray = live ? ray_raw : n_rays - 1;
+    const int T = S + N;
+    float *z = s_z[wv];
+    merge_load(z, z_coarse, z_fine, ray, S, N, lane);
+    __syncthreads();
+    if (!live) return;
+    for (int e = lane; e < T; e += 64) z_out[ray * T + merge_rank(z, T, e)] = z[e];
+}
+
+// the sizes the entries accept
 int importance_sizes(const char *who, int64_t n_rays, int32_t S, int32_t N) {
     NB_REQUIRE(n_rays >= 0 && n_rays < (1ll << 31), "%s: n_rays = %lld (0..2^31 - 1)", who, (long long)n_rays);
     NB_REQUIRE(S >= 3, "%s: n_samples = %d (>= 3: weights[1:-1] must not be empty)", who, S);
@@ -224,5 +236,16 @@ extern "C" int nb_importance_merge(const float *z_coarse, const float *raw_coars
     hipLaunchKernelGGL(importance_merge_kernel, dim3(nb_ceil_div(n_rays, RAYS_PER_BLOCK)), dim3(256), 0, (hipStream_t)stream,
                        z_coarse, raw_coarse, z_fine, raw_fine, keep, (long long)n_rays, n_samples, n_importance, z_vals, raw);
     NB_CHECK_LAUNCH("nb_importance_merge");
+    return NB_OK;
+}
+
+extern "C" int nb_importance_merge_z(const float *z_coarse, const float *z_fine, int64_t n_rays, int32_t n_samples,
+                                     int32_t n_importance, float *z_vals, void *stream) {
+    if (int rc = importance_sizes("nb_importance_merge_z", n_rays, n_samples, n_importance)) return rc;
+    if (n_rays == 0) return NB_OK;
+    NB_REQUIRE(z_coarse && z_fine && z_vals, "nb_importance_merge_z: NULL pointer");
+    hipLaunchKernelGGL(importance_merge_z_kernel, dim3(nb_ceil_div(n_rays, RAYS_PER_BLOCK)), dim3(256), 0, (hipStream_t)stream,
+                       z_coarse, z_fine, (long long)n_rays, n_samples, n_importance, z_vals);
+    NB_CHECK_LAUNCH("nb_importance_merge_z");
     return NB_OK;
 }

@@ -1908,3 +1908,78 @@ def image_undistort(rgb, msk, cam, n=1, fill=None):
         check(_lib.lib().nb_image_undistort(ptr(rgb), ptr(msk), cam.ctypes.data_as(C.POINTER(C.c_double)), V, H, W, n,
                                             _lib.FILL_MODES[fill], ptr(img_out), ptr(msk_out), _stream()), "nb_image_undistort")
     return img_out, msk_out
+
+
+# ------------------------------------------------------------------------------------------- vanilla-NeRF baseline
+NERF_PRECISIONS = {"f32": 0, "f16x3": 2}  # nb_nerf_pack / nb_nerf_decode: NB_PREC_F32, NB_PREC_F16X3
+# one Nerf module's parameters in nb_nerf_params order, as (attribute path, shape)
+NERF_PARAM_SHAPES = [("pts_linears.%d" % i, (256, 63 if i == 0 else (319 if i == 5 else 256))) for i in range(8)] + \
+                    [("views_linears.0", (128, 283)), ("feature_linear", (256, 256)), ("alpha_linear", (1, 256)), ("rgb_linear", (3, 128))]
+
+
+def _nerf_precision(precision):
+    if precision not in NERF_PRECISIONS:
+        raise ValueError("nerf precision must be one of %s, got %r" % (sorted(NERF_PRECISIONS), precision))
+    return NERF_PRECISIONS[precision]
+
+
+def nerf_pack_size(precision="f32"):
+    return int(_lib.lib().nb_nerf_pack_size(_nerf_precision(precision)))
+
+
+def nerf_pack(params, precision="f32", out=None):
+    """nb_nerf_pack: params maps '<layer>.weight' / '<layer>.bias' (the names of one reference Nerf module's state_dict) to fp32
+    device tensors in the reference's shapes -> the packed blob [nerf_pack_size()]."""
+    prec = _nerf_precision(precision)
+    p = _lib.NbNerfParams()
+    dev = None
+    for name, shape in NERF_PARAM_SHAPES:
+        w = _req(params[name + ".weight"], torch.float32, shape, name + ".weight")
+        b = _req(params[name + ".bias"], torch.float32, (shape[0],), name + ".bias")
+        dev = w.device if dev is None else dev
+        if w.device != dev or b.device != dev:
+            raise ValueError("nerf_pack: %s lives on %s, the first parameter on %s" % (name, w.device, dev))
+        if name.startswith("pts_linears."):
+            i = int(name.split(".")[1])
+            p.pts_w[i], p.pts_b[i] = w.data_ptr(), b.data_ptr()
+        else:
+            field = name.split("_")[0]  # views_linears.0 -> views, feature_linear -> feature, ...
+            setattr(p, field + "_w", w.data_ptr())
+            setattr(p, field + "_b", b.data_ptr())
+    if out is None:
+        out = torch.empty(nerf_pack_size(precision), dtype=torch.float32, device=dev)
+    _req(out, torch.float32, (nerf_pack_size(precision),), "out")
+    with torch.cuda.device(dev):
+        check(_lib.lib().nb_nerf_pack(C.byref(p), ptr(out), prec, _stream()), "nb_nerf_pack")
+    return out
+
+
+def nerf_decode(packed, ray_o, ray_d, z_vals, precision="f32", out=None):
+    """nb_nerf_decode: raw [n,S,4] of the packed Nerf module at the depths z_vals [n,S] of the rays ray_o / ray_d [n,3]
+    (points fl32(o + fl32(d z)), direction d / |d|)."""
+    prec = _nerf_precision(precision)
+    _req(z_vals, torch.float32, (None, None), "z_vals")
+    n, S = z_vals.shape
+    _req(ray_o, torch.float32, (n, 3), "ray_o")
+    _req(ray_d, torch.float32, (n, 3), "ray_d")
+    _req(packed, torch.float32, (nerf_pack_size(precision),), "packed")
+    if out is None:
+        out = torch.empty((n, S, 4), dtype=torch.float32, device=z_vals.device)
+    _req(out, torch.float32, (n, S, 4), "out")
+    with torch.cuda.device(z_vals.device):
+        check(_lib.lib().nb_nerf_decode(ptr(packed), ptr(ray_o), ptr(ray_d), ptr(z_vals), n, S, ptr(out), prec, _stream()),
+              "nb_nerf_decode")
+    return out
+
+
+def importance_merge_z(z_coarse, z_fine):
+    """nb_importance_merge_z: z_coarse [n,S] and z_fine [n,N] -> z_vals [n,S+N] sorted by depth (importance_merge's stable rule,
+    depths alone)."""
+    _req(z_coarse, torch.float32, (None, None), "z_coarse")
+    n, S = z_coarse.shape
+    _req(z_fine, torch.float32, (n, None), "z_fine")
+    N = int(z_fine.shape[1])
+    z_vals = torch.empty((n, S + N), dtype=torch.float32, device=z_coarse.device)
+    with torch.cuda.device(z_coarse.device):
+        check(_lib.lib().nb_importance_merge_z(ptr(z_coarse), ptr(z_fine), n, S, N, ptr(z_vals), _stream()), "nb_importance_merge_z")
+    return z_vals
