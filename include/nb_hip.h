@@ -1047,6 +1047,32 @@ int nb_raygen_body(int32_t H, int32_t W, const double K[9], const double R[9], c
  *   baseline's fine pass re-evaluates every merged depth: nb_importance_merge's counting rule (one device function ranks for
  *   both) and sizes, without any raw.  z_coarse [n_rays, n_samples], z_fine [n_rays, n_importance] -> z_vals [n_rays, n_samples +
  *   n_importance].
+ *
+ * Training (opt-in: nothing above changes).  The training forward is NB_PREC_F32 whatever the inference precision is.
+ * nb_nerf_decode_tap — nb_nerf_decode(NB_PREC_F32) that also writes the activation tap: the same raw bit for bit.  tap, dev,
+ *   16-byte aligned, row-major [n_rays * n_samples, NB_NERF_TAP_COLS = 2528] fp32, per sample the columns
+ *     [0, 2048)      h0 .. h7, the outputs of pts_linears[0..7] after the relu, 256 each;
+ *     [2048, 2304)   feature_linear's output;
+ *     [2304, 2432)   V, the output of views_linears[0] after the relu;
+ *     [2432, 2496)   the 63 point-embedding columns in the reference's order, then one zero;
+ *     [2496, 2528)   the 27 direction-embedding columns, then five zeros.
+ *   Every slice is a 16-byte-aligned strided matrix (row stride 10112 bytes) that nb_gemm_fused takes as it is.  Sizes and
+ *   errors as nb_nerf_decode.  One launch.
+ * nb_nerf_pack_bwd_size() — floats of the transposed blob (557696).
+ * nb_nerf_pack_bwd — writes the blob of the input-gradient chain once per parameter version: views_w[:, :256]^T (K = 128),
+ *   feature_w^T, pts_w[7..1]^T (of pts_w[5] its 256 h columns: the 63 input columns of the skip pass no gradient on) in
+ *   nb_nerf_pack's [wave][chunk][feature tile][lane][k-step] fragment order, then rgb_w [3,128] and alpha_w [256] as they are.  Biases
+ *   are not read and may be NULL.  packed_bwd dev, 16-byte aligned.  Ten launches.
+ * nb_nerf_bwd_chain — the gradient of every pre-activation from d_raw [n_pts, 4] (rgb, sigma), the tap (V and h7 .. h0 as relu
+ *   masks: the forward's own stored post-activation values, > 0 passes, exactly 0 does not, as torch.relu) and the blob:
+ *     dV = (rgb_w^T d_rgb) . [V > 0];  dfeat = views_w[:, :256]^T dV;  dz7 = (feature_w^T dfeat + alpha_w^T d_sigma) . [h7 > 0];
+ *     dz_{L-1} = (pts_w[L]^T dz_L) . [h_{L-1} > 0], L = 7 .. 1.
+ *   dtap, dev, 16-byte aligned, row-major [n_pts, NB_NERF_DTAP_COLS = 2432] fp32: [256 i, 256 i + 256) dz_i, i = 0 .. 7;
+ *   [2048, 2304) dfeat; [2304, 2432) dV.  Only rows < n_pts are written.  Exact fp32 fma chains from 0 in ascending k
+ *   (v_mfma_f32_32x32x2_f32; the order is written out at the top of csrc/nb_nerf_bwd.hip), no atomics.  The parameter gradients are
+ *   then dW = dz^T x (nb_gemm_fused, trans_a) and db = column sums of dz (nb_colsum) over slices of the two buffers.
+ *   Sizes, else NB_EINVAL: 0 <= n_pts < 2^37 (n_pts == 0: NB_OK at once, no pointer is looked at).  NULL or misaligned pointers:
+ *   NB_EINVAL with a message.  One launch.
  * ------------------------------------------------------------------------------- */
 #define NB_PREC_F16X3 2 /* nb_nerf_pack / nb_nerf_decode only: fp16 head + remainder, three products, fp32 accumulate */
 typedef struct nb_nerf_params {
@@ -1057,6 +1083,13 @@ int64_t nb_nerf_pack_size(int precision);
 int nb_nerf_pack(const nb_nerf_params *params, float *packed, int precision, void *stream);
 int nb_nerf_decode(const float *packed, const float *ray_o, const float *ray_d, const float *z_vals, int64_t n_rays,
                    int32_t n_samples, float *raw, int precision, void *stream);
+#define NB_NERF_TAP_COLS 2528
+#define NB_NERF_DTAP_COLS 2432
+int nb_nerf_decode_tap(const float *packed, const float *ray_o, const float *ray_d, const float *z_vals, int64_t n_rays,
+                       int32_t n_samples, float *raw, float *tap, void *stream);
+int64_t nb_nerf_pack_bwd_size(void);
+int nb_nerf_pack_bwd(const nb_nerf_params *params, float *packed_bwd, void *stream);
+int nb_nerf_bwd_chain(const float *packed_bwd, const float *tap, const float *d_raw, int64_t n_pts, float *dtap, void *stream);
 int nb_importance_merge_z(const float *z_coarse, const float *z_fine, int64_t n_rays, int32_t n_samples, int32_t n_importance,
                           float *z_vals, void *stream);
 

@@ -177,6 +177,10 @@ SIGNATURES = {
     "nb_nerf_pack_size": (_I64, [C.c_int]),
     "nb_nerf_pack": (C.c_int, [C.POINTER(NbNerfParams), _P, C.c_int, _P]),
     "nb_nerf_decode": (C.c_int, [_P, _P, _P, _P, _I64, _I32, _P, C.c_int, _P]),
+    "nb_nerf_decode_tap": (C.c_int, [_P, _P, _P, _P, _I64, _I32, _P, _P, _P]),
+    "nb_nerf_pack_bwd_size": (_I64, []),
+    "nb_nerf_pack_bwd": (C.c_int, [C.POINTER(NbNerfParams), _P, _P]),
+    "nb_nerf_bwd_chain": (C.c_int, [_P, _P, _P, _I64, _P, _P]),
     "nb_importance_merge_z": (C.c_int, [_P, _P, _I64, _I32, _I32, _P, _P]),
 }
 

@@ -37,15 +37,12 @@
 // heads then eight remainders in the same [wave][chunk][feature tile][lane] order and the same number of bytes as the fp32 blob.
 // Biases, alpha_linear and rgb_linear stay fp32 (fma chains over head + remainder).  The accumulation order inside the MFMA is the
 // hardware's; the result is still a function of the inputs alone.
-#include "nb_march_common.h"
+#include "nb_nerf_mm.h"
 
 namespace {
 
-using namespace nbm;
+using namespace nbnerf;
 
-constexpr int TILE = 64;  // samples per workgroup
-constexpr int ROW_PTS = 256, ROW_VIEW = 320, ROW_ALPHA = 352, N_ROWS = 356;
-constexpr int N_PTS_EMB = 63, N_VIEW_EMB = 27;  // xyz_res 10, view_res 4
 constexpr int LDS_BYTES = N_ROWS * TILE * 4;
 constexpr int STRIDE16 = 360;                  // halves per sample of the fp16 image: 352 rows + 8, so 16-byte reads stay aligned
 constexpr int LO16 = TILE * STRIDE16;          // the remainders' array follows the heads'
@@ -53,34 +50,6 @@ constexpr int ALPHA16 = 2 * LO16 / 2;          // float index of the four alpha_
 constexpr int LDS_BYTES16 = 2 * LO16 * 2 + 4 * TILE * 4;
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-
-// the ten matrix layers: 0..7 pts_linears, 8 feature_linear, 9 views_linears[0]
-constexpr int N_MM = 10, MM_FEATURE = 8, MM_VIEWS = 9, MM_SKIP = 5;
-__host__ __device__ constexpr int mm_out(int L) { return L == MM_VIEWS ? 128 : 256; }
-__host__ __device__ constexpr int mm_in(int L) { return L == 0 ? 63 : (L == MM_SKIP ? 319 : (L == MM_VIEWS ? 283 : 256)); }
-__host__ __device__ constexpr int mm_row0(int L) { return L == 0 ? ROW_PTS : 0; }
-__host__ __device__ constexpr int mm_c0(int L) { return L == 0 ? 4 : 16; }  // chunks (16 rows) of the first segment
-__host__ __device__ constexpr int mm_row1(int L) { return L == MM_SKIP ? ROW_PTS : ROW_VIEW; }
-__host__ __device__ constexpr int mm_c1(int L) { return L == MM_SKIP ? 4 : (L == MM_VIEWS ? 2 : 0); }
-__host__ __device__ constexpr int mm_k(int L) { return 16 * (mm_c0(L) + mm_c1(L)); }
-__host__ __device__ constexpr int mm_w_off(int L) {
-    int o = 0;
-    for (int i = 0; i < L; ++i) o += mm_out(i) * mm_k(i);
-    return o;
-}
-constexpr int W_TOTAL = mm_w_off(N_MM);
-__host__ __device__ constexpr int mm_b_off(int L) { return W_TOTAL + 256 * L; }
-constexpr int OFF_ALPHA_W = mm_b_off(MM_VIEWS) + 128, OFF_ALPHA_B = OFF_ALPHA_W + 256, OFF_RGB_W = OFF_ALPHA_B + 4,
-              OFF_RGB_B = OFF_RGB_W + 384, PACK_FLOATS = OFF_RGB_B + 4;
-static_assert(W_TOTAL == 593920 && W_TOTAL % 4 == 0, "ten matrices, K padded to whole chunks");
-
-// the weight column that row `row` of the LDS image meets in layer L, -1 = a zero row
-__host__ __device__ constexpr int mm_col(int L, int row) {
-    if (L == 0) return row - ROW_PTS < N_PTS_EMB ? row - ROW_PTS : -1;
-    if (L == MM_SKIP) return row < 256 ? N_PTS_EMB + row : (row - ROW_PTS < N_PTS_EMB ? row - ROW_PTS : -1);  // nerf.py:53
-    if (L == MM_VIEWS) return row < 256 ? row : (row - ROW_VIEW < N_VIEW_EMB ? 256 + row - ROW_VIEW : -1);   // nerf.py:58
-    return row;
-}
 
 struct PackArgs {
     const float *w[N_MM], *b[N_MM], *alpha_w, *alpha_b, *rgb_w, *rgb_b;
@@ -129,65 +98,8 @@ struct DecodeArgs {
     long long n_pts;
     int S;
     float *raw;
+    float *tap;  // nerf_decode_kernel<true> only: [n_pts, NT_COLS]
 };
-
-// One matrix layer of this wave: acc[ft][st] = bias + W . act over the layer's row segments.  wp: the wave's packed weights,
-// bias: the bias of the wave's first feature.  The next chunk's fragments are in flight while a chunk's sixteen MFMAs run.
-template <int FT>
-__device__ __forceinline__ void mm_layer(const float *__restrict__ wp, const float *__restrict__ bias, const float *act, int row0,
-                                         int c0, int row1, int c1, f32x16 (&acc)[FT][2], int lane) {
-    const int hi = lane >> 5, col = lane & 31;
-#pragma unroll
-    for (int ft = 0; ft < FT; ++ft)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const float b = bias[32 * ft + tile_row(r, hi)];
-            acc[ft][0][r] = b;
-            acc[ft][1][r] = b;
-        }
-    const f32x4 *wq = reinterpret_cast<const f32x4 *>(wp) + lane * 2;
-    const int C = c0 + c1;
-    f32x4 cur[FT][2], nxt[FT][2];
-#pragma unroll
-    for (int ft = 0; ft < FT; ++ft) cur[ft][0] = wq[ft * 128], cur[ft][1] = wq[ft * 128 + 1];
-    for (int c = 0; c < C; ++c) {
-        const int cn = c + 1 < C ? c + 1 : c;  // (the last chunk reloads itself: no branch around the loads)
-#pragma unroll
-        for (int ft = 0; ft < FT; ++ft) nxt[ft][0] = wq[(cn * FT + ft) * 128], nxt[ft][1] = wq[(cn * FT + ft) * 128 + 1];
-        const int row = c < c0 ? row0 + 16 * c : row1 + 16 * (c - c0);
-        const float *b = act + (row + hi) * TILE + col;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            const float b0 = b[2 * e * TILE], b1 = b[2 * e * TILE + 32];
-#pragma unroll
-            for (int ft = 0; ft < FT; ++ft) {
-                const float w = cur[ft][e >> 2][e & 3];
-                acc[ft][0] = NB_MFMA(w, b0, acc[ft][0]);
-                acc[ft][1] = NB_MFMA(w, b1, acc[ft][1]);
-            }
-        }
-#pragma unroll
-        for (int ft = 0; ft < FT; ++ft) cur[ft][0] = nxt[ft][0], cur[ft][1] = nxt[ft][1];
-    }
-}
-
-// The wave's tiles go to rows [f0, f0 + 32 FT) of the image, between two barriers: every wave has read the old rows before any
-// wave writes, and every row is written before the next layer reads.
-template <int FT, bool RELU>
-__device__ __forceinline__ void publish(const f32x16 (&acc)[FT][2], float *act, int f0, int lane) {
-    const int hi = lane >> 5, col = lane & 31;
-    __syncthreads();
-#pragma unroll
-    for (int ft = 0; ft < FT; ++ft)
-#pragma unroll
-        for (int st = 0; st < 2; ++st)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const float v = acc[ft][st][r];
-                act[(f0 + 32 * ft + tile_row(r, hi)) * TILE + 32 * st + col] = RELU ? fmaxf(v, 0.f) : v;
-            }
-    __syncthreads();
-}
 
 // embedding column e of one 3-vector (embedder.py:26-36): x, then per frequency the three sines and the three cosines
 __device__ __forceinline__ float embed_col(int e, const float (&x)[3], const double (&t)[3]) {
@@ -197,6 +109,9 @@ __device__ __forceinline__ float embed_col(int e, const float (&x)[3], const dou
     return sin_rev(ta * (double)(1 << f) + (rem >= 3 ? 0.25 : 0.0));
 }
 
+// TAP: also write the sample's row of the activation tap (nb_nerf_mm.h), every value as the next layer reads it.  The arithmetic
+// does not depend on TAP: a layer's D fragments go to the tap from the registers that publish() writes to the image.
+template <bool TAP>
 __global__ __launch_bounds__(256) void nerf_decode_kernel(DecodeArgs a) {
     extern __shared__ __attribute__((aligned(16))) float act[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -204,6 +119,13 @@ __global__ __launch_bounds__(256) void nerf_decode_kernel(DecodeArgs a) {
     const long long pt_raw = (long long)blockIdx.x * TILE + s;
     const bool live = pt_raw < a.n_pts;
     const long long pt = live ? pt_raw : a.n_pts - 1;  // a padding sample repeats the last point and stores nothing
+    // the tap rows of the two samples whose D fragments this lane holds (sample tiles 0 and 1), NULL = padding
+    float *tap0 = nullptr, *tap1 = nullptr;
+    if constexpr (TAP) {
+        const long long p0 = (long long)blockIdx.x * TILE + (lane & 31);
+        if (p0 < a.n_pts) tap0 = a.tap + p0 * NT_COLS;
+        if (p0 + 32 < a.n_pts) tap1 = a.tap + (p0 + 32) * NT_COLS;
+    }
     {
         const long long ray = pt / a.S;
         const float z = a.z_vals[pt];
@@ -218,6 +140,16 @@ __global__ __launch_bounds__(256) void nerf_decode_kernel(DecodeArgs a) {
         for (int e = q; e < 32; e += 4) act[(ROW_VIEW + e) * TILE + s] = e < N_VIEW_EMB ? embed_col(e, v, tv) : 0.f;
     }
     __syncthreads();
+    if constexpr (TAP) {  // the embeddings: thread (s, q) copies columns [24 q, 24 q + 24) of its sample's 96, 16 bytes at a time
+        if (live) {
+            float *dst = a.tap + pt * NT_COLS + NT_PTS;
+            for (int c = 24 * q; c < 24 * q + 24; c += 4) {
+                f32x4 v;
+                for (int i = 0; i < 4; ++i) v[i] = act[(ROW_PTS + c + i) * TILE + s];
+                *reinterpret_cast<f32x4 *>(dst + c) = v;
+            }
+        }
+    }
 
     const float *pk = a.packed;
     f32x16 acc[2][2];
@@ -231,6 +163,11 @@ __global__ __launch_bounds__(256) void nerf_decode_kernel(DecodeArgs a) {
         }
         mm_layer<2>(pk + mm_w_off(L) + wave * (mm_k(L) * 64), pk + mm_b_off(L) + 64 * wave, act, mm_row0(L), mm_c0(L), mm_row1(L),
                     mm_c1(L), acc, lane);
+        if constexpr (TAP) {  // layer L's columns start at 256 L: NT_H + 256 L for h, NT_FEATURE = 256 MM_FEATURE
+            const int c = 256 * L + 64 * wave;
+            if (L == MM_FEATURE) store_rows<2, false>(acc, tap0 ? tap0 + c : nullptr, tap1 ? tap1 + c : nullptr, lane);
+            else store_rows<2, true>(acc, tap0 ? tap0 + c : nullptr, tap1 ? tap1 + c : nullptr, lane);
+        }
         if (L == MM_FEATURE) publish<2, false>(acc, act, 64 * wave, lane);
         else publish<2, true>(acc, act, 64 * wave, lane);
     }
@@ -238,6 +175,10 @@ __global__ __launch_bounds__(256) void nerf_decode_kernel(DecodeArgs a) {
         f32x16 accv[1][2];
         mm_layer<1>(pk + mm_w_off(MM_VIEWS) + wave * (mm_k(MM_VIEWS) * 32), pk + mm_b_off(MM_VIEWS) + 32 * wave, act,
                     mm_row0(MM_VIEWS), mm_c0(MM_VIEWS), mm_row1(MM_VIEWS), mm_c1(MM_VIEWS), accv, lane);
+        if constexpr (TAP) {
+            const int c = NT_V + 32 * wave;
+            store_rows<1, true>(accv, tap0 ? tap0 + c : nullptr, tap1 ? tap1 + c : nullptr, lane);
+        }
         publish<1, true>(accv, act, 32 * wave, lane);
     }
     float out;
@@ -422,26 +363,42 @@ extern "C" int nb_nerf_pack(const nb_nerf_params *params, float *packed, int pre
     return NB_OK;
 }
 
+// the checks nb_nerf_decode and nb_nerf_decode_tap share; tap NULL = no tap (f32 or f16x3), else the f32 kernel with the tap
+static int nerf_decode_launch(const char *who, const float *packed, const float *ray_o, const float *ray_d, const float *z_vals,
+                              int64_t n_rays, int32_t n_samples, float *raw, float *tap, bool want_tap, int precision, void *stream) {
+    NB_REQUIRE(n_rays >= 0 && n_rays < (1ll << 31), "%s: n_rays = %lld (0..2^31 - 1)", who, (long long)n_rays);
+    NB_REQUIRE(n_samples >= 1 && n_samples <= 512, "%s: n_samples = %d (1..512)", who, n_samples);
+    if (n_rays == 0) return NB_OK;
+    NB_REQUIRE(packed && ray_o && ray_d && z_vals && raw && (tap || !want_tap), "%s: NULL pointer", who);
+    NB_REQUIRE(((uintptr_t)packed & 15) == 0 && ((uintptr_t)tap & 15) == 0, "%s: packed%s must be 16-byte aligned", who,
+               want_tap ? " and tap" : "");
+    NB_REQUIRE((((uintptr_t)ray_o | (uintptr_t)ray_d | (uintptr_t)z_vals | (uintptr_t)raw) & 3) == 0,
+               "%s: ray_o, ray_d, z_vals and raw must be 4-byte aligned", who);
+    const long long n_pts = (long long)n_rays * n_samples;
+    NB_REQUIRE(n_pts / TILE < (1ll << 31) - 1, "%s: n_rays * n_samples = %lld (< 2^37)", who, n_pts);
+    // the attribute belongs to (function, device): set on every call, whichever device and thread this is (a host-side table write)
+    const bool fast = precision == NB_PREC_F16X3;
+    const void *fn = fast       ? reinterpret_cast<const void *>(nerf_decode16_kernel)
+                     : want_tap ? reinterpret_cast<const void *>(nerf_decode_kernel<true>)
+                                : reinterpret_cast<const void *>(nerf_decode_kernel<false>);
+    const int lds = fast ? LDS_BYTES16 : LDS_BYTES;
+    NB_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    DecodeArgs a = {packed, ray_o, ray_d, z_vals, n_pts, n_samples, raw, tap};
+    const dim3 grid(nb_ceil_div(n_pts, TILE));
+    if (fast) hipLaunchKernelGGL(nerf_decode16_kernel, grid, dim3(256), lds, (hipStream_t)stream, a);
+    else if (want_tap) hipLaunchKernelGGL(nerf_decode_kernel<true>, grid, dim3(256), lds, (hipStream_t)stream, a);
+    else hipLaunchKernelGGL(nerf_decode_kernel<false>, grid, dim3(256), lds, (hipStream_t)stream, a);
+    NB_CHECK_LAUNCH(who);
+    return NB_OK;
+}
+
 extern "C" int nb_nerf_decode(const float *packed, const float *ray_o, const float *ray_d, const float *z_vals, int64_t n_rays,
                               int32_t n_samples, float *raw, int precision, void *stream) {
     if (int rc = nerf_precision("nb_nerf_decode", precision)) return rc;
-    NB_REQUIRE(n_rays >= 0 && n_rays < (1ll << 31), "nb_nerf_decode: n_rays = %lld (0..2^31 - 1)", (long long)n_rays);
-    NB_REQUIRE(n_samples >= 1 && n_samples <= 512, "nb_nerf_decode: n_samples = %d (1..512)", n_samples);
-    if (n_rays == 0) return NB_OK;
-    NB_REQUIRE(packed && ray_o && ray_d && z_vals && raw, "nb_nerf_decode: NULL pointer");
-    NB_REQUIRE(((uintptr_t)packed & 15) == 0, "nb_nerf_decode: packed must be 16-byte aligned");
-    NB_REQUIRE((((uintptr_t)ray_o | (uintptr_t)ray_d | (uintptr_t)z_vals | (uintptr_t)raw) & 3) == 0,
-               "nb_nerf_decode: ray_o, ray_d, z_vals and raw must be 4-byte aligned");
-    const long long n_pts = (long long)n_rays * n_samples;
-    NB_REQUIRE(n_pts / TILE < (1ll << 31) - 1, "nb_nerf_decode: n_rays * n_samples = %lld (< 2^37)", n_pts);
-    // the attribute belongs to (function, device): set on every call, whichever device and thread this is (a host-side table write)
-    const bool fast = precision == NB_PREC_F16X3;
-    const void *fn = fast ? reinterpret_cast<const void *>(nerf_decode16_kernel) : reinterpret_cast<const void *>(nerf_decode_kernel);
-    const int lds = fast ? LDS_BYTES16 : LDS_BYTES;
-    NB_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    DecodeArgs a = {packed, ray_o, ray_d, z_vals, n_pts, n_samples, raw};
-    if (fast) hipLaunchKernelGGL(nerf_decode16_kernel, dim3(nb_ceil_div(n_pts, TILE)), dim3(256), lds, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL(nerf_decode_kernel, dim3(nb_ceil_div(n_pts, TILE)), dim3(256), lds, (hipStream_t)stream, a);
-    NB_CHECK_LAUNCH("nb_nerf_decode");
-    return NB_OK;
+    return nerf_decode_launch("nb_nerf_decode", packed, ray_o, ray_d, z_vals, n_rays, n_samples, raw, nullptr, false, precision, stream);
+}
+
+extern "C" int nb_nerf_decode_tap(const float *packed, const float *ray_o, const float *ray_d, const float *z_vals, int64_t n_rays,
+                                  int32_t n_samples, float *raw, float *tap, void *stream) {
+    return nerf_decode_launch("nb_nerf_decode_tap", packed, ray_o, ray_d, z_vals, n_rays, n_samples, raw, tap, true, NB_PREC_F32, stream);
 }

@@ -1972,6 +1972,78 @@ def nerf_decode(packed, ray_o, ray_d, z_vals, precision="f32", out=None):
     return out
 
 
+NERF_TAP_COLS, NERF_DTAP_COLS = 2528, 2432  # NB_NERF_TAP_COLS, NB_NERF_DTAP_COLS
+# column slices of the tap (include/nb_hip.h: nb_nerf_decode_tap) and of the d-tap (nb_nerf_bwd_chain), as (first, width)
+NERF_TAP = {"h": lambda i: (256 * i, 256), "feature": (2048, 256), "V": (2304, 128), "pts": (2432, 63), "view": (2496, 27)}
+NERF_DTAP = {"z": lambda i: (256 * i, 256), "feature": (2048, 256), "V": (2304, 128)}
+
+
+def nerf_decode_tap(packed, ray_o, ray_d, z_vals, out=None, tap=None):
+    """nb_nerf_decode_tap: (raw [n,S,4], tap [n*S, NERF_TAP_COLS]) of the f32-packed Nerf module: nerf_decode(..., 'f32')'s raw bit
+    for bit plus every activation the backward needs (the training forward)."""
+    _req(z_vals, torch.float32, (None, None), "z_vals")
+    n, S = z_vals.shape
+    _req(ray_o, torch.float32, (n, 3), "ray_o")
+    _req(ray_d, torch.float32, (n, 3), "ray_d")
+    _req(packed, torch.float32, (nerf_pack_size("f32"),), "packed")
+    if out is None:
+        out = torch.empty((n, S, 4), dtype=torch.float32, device=z_vals.device)
+    _req(out, torch.float32, (n, S, 4), "out")
+    if tap is None:
+        tap = torch.empty((n * S, NERF_TAP_COLS), dtype=torch.float32, device=z_vals.device)
+    _req(tap, torch.float32, (n * S, NERF_TAP_COLS), "tap")
+    with torch.cuda.device(z_vals.device):
+        check(_lib.lib().nb_nerf_decode_tap(ptr(packed), ptr(ray_o), ptr(ray_d), ptr(z_vals), n, S, ptr(out), ptr(tap), _stream()),
+              "nb_nerf_decode_tap")
+    return out, tap
+
+
+def nerf_pack_bwd_size():
+    return int(_lib.lib().nb_nerf_pack_bwd_size())
+
+
+def nerf_pack_bwd(params, out=None):
+    """nb_nerf_pack_bwd: params as for nerf_pack (the biases are not read) -> the transposed blob [nerf_pack_bwd_size()] of the
+    input-gradient chain."""
+    p = _lib.NbNerfParams()
+    dev = None
+    for name, shape in NERF_PARAM_SHAPES:
+        w = _req(params[name + ".weight"], torch.float32, shape, name + ".weight")
+        dev = w.device if dev is None else dev
+        if w.device != dev:
+            raise ValueError("nerf_pack_bwd: %s lives on %s, the first parameter on %s" % (name, w.device, dev))
+        if name.startswith("pts_linears."):
+            p.pts_w[int(name.split(".")[1])] = w.data_ptr()
+        else:
+            setattr(p, name.split("_")[0] + "_w", w.data_ptr())
+    if out is None:
+        out = torch.empty(nerf_pack_bwd_size(), dtype=torch.float32, device=dev)
+    _req(out, torch.float32, (nerf_pack_bwd_size(),), "out")
+    with torch.cuda.device(dev):
+        check(_lib.lib().nb_nerf_pack_bwd(C.byref(p), ptr(out), _stream()), "nb_nerf_pack_bwd")
+    return out
+
+
+def nerf_bwd_chain(packed_bwd, tap, d_raw, dtap=None):
+    """nb_nerf_bwd_chain: d_raw [n_pts,4] (or [n,S,4]) and the forward's tap [n_pts, NERF_TAP_COLS] -> the d-tap
+    [n_pts, NERF_DTAP_COLS], the gradient of every pre-activation.  A given dtap may have more rows: only the first n_pts are
+    written."""
+    _req(tap, torch.float32, (None, NERF_TAP_COLS), "tap")
+    n_pts = tap.shape[0]
+    _req(d_raw, torch.float32, None, "d_raw")
+    if d_raw.numel() != n_pts * 4 or d_raw.shape[-1] != 4:
+        raise ValueError("d_raw must hold [%d, 4] values, got %s" % (n_pts, tuple(d_raw.shape)))
+    _req(packed_bwd, torch.float32, (nerf_pack_bwd_size(),), "packed_bwd")
+    if dtap is None:
+        dtap = torch.empty((n_pts, NERF_DTAP_COLS), dtype=torch.float32, device=tap.device)
+    _req(dtap, torch.float32, (None, NERF_DTAP_COLS), "dtap")
+    if dtap.shape[0] < n_pts:
+        raise ValueError("dtap has %d rows, the tap %d" % (dtap.shape[0], n_pts))
+    with torch.cuda.device(tap.device):
+        check(_lib.lib().nb_nerf_bwd_chain(ptr(packed_bwd), ptr(tap), ptr(d_raw), n_pts, ptr(dtap), _stream()), "nb_nerf_bwd_chain")
+    return dtap
+
+
 def importance_merge_z(z_coarse, z_fine):
     """nb_importance_merge_z: z_coarse [n,S] and z_fine [n,N] -> z_vals [n,S+N] sorted by depth (importance_merge's stable rule,
     depths alone)."""
