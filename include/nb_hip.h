@@ -1073,6 +1073,24 @@ int nb_raygen_body(int32_t H, int32_t W, const double K[9], const double R[9], c
  *   then dW = dz^T x (nb_gemm_fused, trans_a) and db = column sums of dz (nb_colsum) over slices of the two buffers.
  *   Sizes, else NB_EINVAL: 0 <= n_pts < 2^37 (n_pts == 0: NB_OK at once, no pointer is looked at).  NULL or misaligned pointers:
  *   NB_EINVAL with a message.  One launch.
+ *
+ * The baseline's mesh pass (lib/networks/nerf_mesh.py behind lib/networks/renderer/volume_mesh_renderer.py): a density at points.
+ * nb_nerf_density — alpha [n] = alpha_linear(h7) at the points pts [n, 3], the trunk of the MLP alone (nerf_mesh.py:45-54:
+ *   pts_linears[0..7] with the skip, then alpha_linear; no feature_linear, no view layer, no colour head, no direction).  packed is
+ *   nb_nerf_pack's blob for the same precision (NB_PREC_F32 or NB_PREC_F16X3): there is no other pack format.  The kernels are
+ *   nb_nerf_decode's with the view rows, layers 8 and 9 and the colour head left out: the same 64-sample workgroup, the same LDS
+ *   image, the same summation order of every layer and of alpha_linear (four 64-column chains, (p0 + p1) + (p2 + p3), then the
+ *   bias), so alpha[i] has the bits of nb_nerf_decode's raw[..., 3] at the same fp32 point, in both arithmetics.  The point is read as
+ *   given (nb_nerf_decode forms fl32(o + fl32(d z)); a ray of depth 0 gives o).  Raw alpha_linear output: no relu.
+ *   Sizes, else NB_EINVAL: 0 <= n < 2^37 (n == 0: NB_OK at once).  NULL pointers, a packed that is not 16-byte aligned, pts or alpha
+ *   not 4-byte aligned, another precision: NB_EINVAL with a message.  One launch, no atomics.
+ * nb_nerf_embed_grad — the last step of d alpha / d p: from the gradient d_emb by the 63 point-embedding columns and the forward's
+ *   own stored columns emb (x, then per frequency f < 10 the three sines and the three cosines, embedder.py:26-36), per axis a
+ *     grad[a] = d_emb[a] + sum_f 2^f (d_emb[3 + 6 f + a] emb[3 + 6 f + 3 + a] - d_emb[3 + 6 f + 3 + a] emb[3 + 6 f + a]),
+ *   accumulated in float64 in ascending f (every product of two fp32 is exact there) and rounded once.  emb and d_emb are row-major
+ *   with strides emb_stride and d_stride in floats (>= 63; the tap's columns NB_NERF_TAP_PTS.. with stride NB_NERF_TAP_COLS serve
+ *   as emb), grad dev [n, 3].  One thread per point, no atomics.  0 <= n < 2^39 (n == 0: NB_OK at once); NULL or pointers that are
+ *   not 4-byte aligned, a stride below 63: NB_EINVAL.  One launch.
  * ------------------------------------------------------------------------------- */
 #define NB_PREC_F16X3 2 /* nb_nerf_pack / nb_nerf_decode only: fp16 head + remainder, three products, fp32 accumulate */
 typedef struct nb_nerf_params {
@@ -1092,6 +1110,10 @@ int nb_nerf_pack_bwd(const nb_nerf_params *params, float *packed_bwd, void *stre
 int nb_nerf_bwd_chain(const float *packed_bwd, const float *tap, const float *d_raw, int64_t n_pts, float *dtap, void *stream);
 int nb_importance_merge_z(const float *z_coarse, const float *z_fine, int64_t n_rays, int32_t n_samples, int32_t n_importance,
                           float *z_vals, void *stream);
+#define NB_NERF_TAP_PTS 2432 /* first column of the point embedding in the tap */
+int nb_nerf_density(const float *packed, const float *pts, int64_t n, float *alpha, int precision, void *stream);
+int nb_nerf_embed_grad(const float *emb, int64_t emb_stride, const float *d_emb, int64_t d_stride, int64_t n, float *grad,
+                       void *stream);
 
 #ifdef __cplusplus
 }

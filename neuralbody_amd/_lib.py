@@ -182,6 +182,8 @@ SIGNATURES = {
     "nb_nerf_pack_bwd": (C.c_int, [C.POINTER(NbNerfParams), _P, _P]),
     "nb_nerf_bwd_chain": (C.c_int, [_P, _P, _P, _I64, _P, _P]),
     "nb_importance_merge_z": (C.c_int, [_P, _P, _I64, _I32, _I32, _P, _P]),
+    "nb_nerf_density": (C.c_int, [_P, _P, _I64, _P, C.c_int, _P]),
+    "nb_nerf_embed_grad": (C.c_int, [_P, _I64, _P, _I64, _I64, _P, _P]),
 }
 
 _lib = None

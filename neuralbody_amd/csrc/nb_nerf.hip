@@ -94,10 +94,10 @@ __global__ __launch_bounds__(256) void nerf_pack_kernel(PackArgs a, int L, int f
 }
 
 struct DecodeArgs {
-    const float *packed, *ray_o, *ray_d, *z_vals;
+    const float *packed, *ray_o, *ray_d, *z_vals;  // DENSITY: ray_o is the points [n_pts,3], ray_d and z_vals are not read
     long long n_pts;
     int S;
-    float *raw;
+    float *raw;  // [n_pts, 4]; DENSITY: alpha [n_pts]
     float *tap;  // nerf_decode_kernel<true> only: [n_pts, NT_COLS]
 };
 
@@ -109,9 +109,29 @@ __device__ __forceinline__ float embed_col(int e, const float (&x)[3], const dou
     return sin_rev(ta * (double)(1 << f) + (rem >= 3 ? 0.25 : 0.0));
 }
 
+// The tile's sample (s, q) of the element-wise phases: the point and, unless DENSITY, the unit direction.  DENSITY reads the point as
+// it is given (no ray, no depth) and has no direction: the trunk does not read one (nerf_mesh.py:45-54).
+template <bool DENSITY>
+__device__ __forceinline__ void sample_inputs(const DecodeArgs &a, long long pt, float (&p)[3], float (&v)[3]) {
+    if constexpr (DENSITY) {
+        p[0] = a.ray_o[pt * 3], p[1] = a.ray_o[pt * 3 + 1], p[2] = a.ray_o[pt * 3 + 2];
+        v[0] = v[1] = v[2] = 0.f;
+    } else {
+        const long long ray = pt / a.S;
+        const float z = a.z_vals[pt];
+        const float dx = a.ray_d[ray * 3], dy = a.ray_d[ray * 3 + 1], dz = a.ray_d[ray * 3 + 2];
+        p[0] = ray_point(a.ray_o[ray * 3], dx, z), p[1] = ray_point(a.ray_o[ray * 3 + 1], dy, z),
+        p[2] = ray_point(a.ray_o[ray * 3 + 2], dz, z);
+        const double dn = sqrt((double)dx * dx + (double)dy * dy + (double)dz * dz);
+        v[0] = (float)((double)dx / dn), v[1] = (float)((double)dy / dn), v[2] = (float)((double)dz / dn);
+    }
+}
+
 // TAP: also write the sample's row of the activation tap (nb_nerf_mm.h), every value as the next layer reads it.  The arithmetic
 // does not depend on TAP: a layer's D fragments go to the tap from the registers that publish() writes to the image.
-template <bool TAP>
+// DENSITY (nb_nerf_density): the trunk alone.  The same image, layers 0..7 by the same mm_layer / publish, then alpha_linear's four
+// chains on h7 and their sum: what raw[..., 3] goes through above, so the same bits.  No view rows, no feature_linear, no heads.
+template <bool TAP, bool DENSITY = false>
 __global__ __launch_bounds__(256) void nerf_decode_kernel(DecodeArgs a) {
     extern __shared__ __attribute__((aligned(16))) float act[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -127,17 +147,14 @@ __global__ __launch_bounds__(256) void nerf_decode_kernel(DecodeArgs a) {
         if (p0 + 32 < a.n_pts) tap1 = a.tap + (p0 + 32) * NT_COLS;
     }
     {
-        const long long ray = pt / a.S;
-        const float z = a.z_vals[pt];
-        const float dx = a.ray_d[ray * 3], dy = a.ray_d[ray * 3 + 1], dz = a.ray_d[ray * 3 + 2];
-        const float p[3] = {ray_point(a.ray_o[ray * 3], dx, z), ray_point(a.ray_o[ray * 3 + 1], dy, z),
-                            ray_point(a.ray_o[ray * 3 + 2], dz, z)};
-        const double dn = sqrt((double)dx * dx + (double)dy * dy + (double)dz * dz);
-        const float v[3] = {(float)((double)dx / dn), (float)((double)dy / dn), (float)((double)dz / dn)};
+        float p[3], v[3];
+        sample_inputs<DENSITY>(a, pt, p, v);
         const double tp[3] = {(double)p[0] * NB_INV_2PI, (double)p[1] * NB_INV_2PI, (double)p[2] * NB_INV_2PI};
-        const double tv[3] = {(double)v[0] * NB_INV_2PI, (double)v[1] * NB_INV_2PI, (double)v[2] * NB_INV_2PI};
         for (int e = q; e < 64; e += 4) act[(ROW_PTS + e) * TILE + s] = e < N_PTS_EMB ? embed_col(e, p, tp) : 0.f;
-        for (int e = q; e < 32; e += 4) act[(ROW_VIEW + e) * TILE + s] = e < N_VIEW_EMB ? embed_col(e, v, tv) : 0.f;
+        if constexpr (!DENSITY) {
+            const double tv[3] = {(double)v[0] * NB_INV_2PI, (double)v[1] * NB_INV_2PI, (double)v[2] * NB_INV_2PI};
+            for (int e = q; e < 32; e += 4) act[(ROW_VIEW + e) * TILE + s] = e < N_VIEW_EMB ? embed_col(e, v, tv) : 0.f;
+        }
     }
     __syncthreads();
     if constexpr (TAP) {  // the embeddings: thread (s, q) copies columns [24 q, 24 q + 24) of its sample's 96, 16 bytes at a time
@@ -153,14 +170,19 @@ __global__ __launch_bounds__(256) void nerf_decode_kernel(DecodeArgs a) {
 
     const float *pk = a.packed;
     f32x16 acc[2][2];
+    const auto alpha_partial = [&]() {  // thread (s, q): alpha_linear's chain over columns [64 q, 64 q + 64) of h7
+        const float *aw = pk + OFF_ALPHA_W + 64 * q;
+        float sum = 0.f;
+        for (int k = 0; k < 64; ++k) sum = fmaf(aw[k], act[(64 * q + k) * TILE + s], sum);
+        act[(ROW_ALPHA + q) * TILE + s] = sum;
+    };
+    const auto alpha_sum = [&]() {
+        const float *pa = act + ROW_ALPHA * TILE + s;
+        return __fadd_rn(__fadd_rn(__fadd_rn(pa[0], pa[TILE]), __fadd_rn(pa[2 * TILE], pa[3 * TILE])), pk[OFF_ALPHA_B]);
+    };
 #pragma unroll 1
-    for (int L = 0; L < MM_VIEWS; ++L) {  // pts_linears[0..7] with relu, then feature_linear without
-        if (L == MM_FEATURE) {            // alpha_linear reads h before feature_linear's publish overwrites it
-            const float *aw = pk + OFF_ALPHA_W + 64 * q;
-            float sum = 0.f;
-            for (int k = 0; k < 64; ++k) sum = fmaf(aw[k], act[(64 * q + k) * TILE + s], sum);
-            act[(ROW_ALPHA + q) * TILE + s] = sum;
-        }
+    for (int L = 0; L < (DENSITY ? MM_FEATURE : MM_VIEWS); ++L) {  // pts_linears[0..7] with relu, then feature_linear without
+        if (L == MM_FEATURE) alpha_partial();  // alpha_linear reads h before feature_linear's publish overwrites it
         mm_layer<2>(pk + mm_w_off(L) + wave * (mm_k(L) * 64), pk + mm_b_off(L) + 64 * wave, act, mm_row0(L), mm_c0(L), mm_row1(L),
                     mm_c1(L), acc, lane);
         if constexpr (TAP) {  // layer L's columns start at 256 L: NT_H + 256 L for h, NT_FEATURE = 256 MM_FEATURE
@@ -170,6 +192,12 @@ __global__ __launch_bounds__(256) void nerf_decode_kernel(DecodeArgs a) {
         }
         if (L == MM_FEATURE) publish<2, false>(acc, act, 64 * wave, lane);
         else publish<2, true>(acc, act, 64 * wave, lane);
+    }
+    if constexpr (DENSITY) {  // h7 is published: the four chains, a barrier, one thread per sample adds them
+        alpha_partial();
+        __syncthreads();
+        if (q == 0 && live) a.raw[pt] = alpha_sum();
+        return;
     }
     {
         f32x16 accv[1][2];
@@ -187,8 +215,7 @@ __global__ __launch_bounds__(256) void nerf_decode_kernel(DecodeArgs a) {
         out = pk[OFF_RGB_B + q];
         for (int k = 0; k < 128; ++k) out = fmaf(rw[k], act[k * TILE + s], out);
     } else {  // alpha_linear's four partial sums
-        const float *pa = act + ROW_ALPHA * TILE + s;
-        out = __fadd_rn(__fadd_rn(__fadd_rn(pa[0], pa[TILE]), __fadd_rn(pa[2 * TILE], pa[3 * TILE])), pk[OFF_ALPHA_B]);
+        out = alpha_sum();
     }
     if (live) a.raw[pt * 4 + q] = out;
 }
@@ -271,6 +298,7 @@ __device__ __forceinline__ void publish16(const f32x16 (&acc)[FT][2], _Float16 *
     __syncthreads();
 }
 
+template <bool DENSITY = false>
 __global__ __launch_bounds__(256) void nerf_decode16_kernel(DecodeArgs a) {
     extern __shared__ __attribute__((aligned(16))) float act[];
     _Float16 *act16 = reinterpret_cast<_Float16 *>(act);
@@ -280,34 +308,42 @@ __global__ __launch_bounds__(256) void nerf_decode16_kernel(DecodeArgs a) {
     const bool live = pt_raw < a.n_pts;
     const long long pt = live ? pt_raw : a.n_pts - 1;
     {
-        const long long ray = pt / a.S;
-        const float z = a.z_vals[pt];
-        const float dx = a.ray_d[ray * 3], dy = a.ray_d[ray * 3 + 1], dz = a.ray_d[ray * 3 + 2];
-        const float p[3] = {ray_point(a.ray_o[ray * 3], dx, z), ray_point(a.ray_o[ray * 3 + 1], dy, z),
-                            ray_point(a.ray_o[ray * 3 + 2], dz, z)};
-        const double dn = sqrt((double)dx * dx + (double)dy * dy + (double)dz * dz);
-        const float v[3] = {(float)((double)dx / dn), (float)((double)dy / dn), (float)((double)dz / dn)};
+        float p[3], v[3];
+        sample_inputs<DENSITY>(a, pt, p, v);
         const double tp[3] = {(double)p[0] * NB_INV_2PI, (double)p[1] * NB_INV_2PI, (double)p[2] * NB_INV_2PI};
-        const double tv[3] = {(double)v[0] * NB_INV_2PI, (double)v[1] * NB_INV_2PI, (double)v[2] * NB_INV_2PI};
         for (int e = q; e < 64; e += 4) put16(act16, ROW_PTS + e, s, e < N_PTS_EMB ? embed_col(e, p, tp) : 0.f);
-        for (int e = q; e < 32; e += 4) put16(act16, ROW_VIEW + e, s, e < N_VIEW_EMB ? embed_col(e, v, tv) : 0.f);
+        if constexpr (!DENSITY) {
+            const double tv[3] = {(double)v[0] * NB_INV_2PI, (double)v[1] * NB_INV_2PI, (double)v[2] * NB_INV_2PI};
+            for (int e = q; e < 32; e += 4) put16(act16, ROW_VIEW + e, s, e < N_VIEW_EMB ? embed_col(e, v, tv) : 0.f);
+        }
     }
     __syncthreads();
 
     const float *pk = a.packed;
     f32x16 acc[2][2];
+    const auto alpha_partial = [&]() {
+        const float *aw = pk + OFF_ALPHA_W + 64 * q;
+        float sum = 0.f;
+        for (int k = 0; k < 64; ++k) sum = fmaf(aw[k], get16(act16, 64 * q + k, s), sum);
+        act[ALPHA16 + q * TILE + s] = sum;
+    };
+    const auto alpha_sum = [&]() {
+        const float *pa = act + ALPHA16 + s;
+        return __fadd_rn(__fadd_rn(__fadd_rn(pa[0], pa[TILE]), __fadd_rn(pa[2 * TILE], pa[3 * TILE])), pk[OFF_ALPHA_B]);
+    };
 #pragma unroll 1
-    for (int L = 0; L < MM_VIEWS; ++L) {
-        if (L == MM_FEATURE) {
-            const float *aw = pk + OFF_ALPHA_W + 64 * q;
-            float sum = 0.f;
-            for (int k = 0; k < 64; ++k) sum = fmaf(aw[k], get16(act16, 64 * q + k, s), sum);
-            act[ALPHA16 + q * TILE + s] = sum;
-        }
+    for (int L = 0; L < (DENSITY ? MM_FEATURE : MM_VIEWS); ++L) {
+        if (L == MM_FEATURE) alpha_partial();
         mm_layer16<2>(pk + mm_w_off(L) + wave * (mm_k(L) * 64), pk + mm_b_off(L) + 64 * wave, act16, mm_row0(L), mm_c0(L),
                       mm_row1(L), mm_c1(L), acc, lane);
         if (L == MM_FEATURE) publish16<2, false>(acc, act16, 64 * wave, lane);
         else publish16<2, true>(acc, act16, 64 * wave, lane);
+    }
+    if constexpr (DENSITY) {
+        alpha_partial();
+        __syncthreads();
+        if (q == 0 && live) a.raw[pt] = alpha_sum();
+        return;
     }
     {
         f32x16 accv[1][2];
@@ -321,10 +357,29 @@ __global__ __launch_bounds__(256) void nerf_decode16_kernel(DecodeArgs a) {
         out = pk[OFF_RGB_B + q];
         for (int k = 0; k < 128; ++k) out = fmaf(rw[k], get16(act16, k, s), out);
     } else {
-        const float *pa = act + ALPHA16 + s;
-        out = __fadd_rn(__fadd_rn(__fadd_rn(pa[0], pa[TILE]), __fadd_rn(pa[2 * TILE], pa[3 * TILE])), pk[OFF_ALPHA_B]);
+        out = alpha_sum();
     }
     if (live) a.raw[pt * 4 + q] = out;
+}
+
+// d alpha / d p from the gradient by the 63 embedding columns (embedder.py:26-36): column a is the coordinate itself, columns
+// 3 + 6 f + a and 3 + 6 f + 3 + a are sin(2^f x_a) and cos(2^f x_a), whose derivatives 2^f cos and -2^f sin are the forward's own stored
+// columns.  One thread per point; every product of two fp32 is exact in float64, the sum runs in float64 in ascending f and is rounded
+// once (as nb_ray_distortion does).
+__global__ __launch_bounds__(256) void nerf_embed_grad_kernel(const float *__restrict__ emb, long long emb_stride,
+                                                              const float *__restrict__ d_emb, long long d_stride, long long n,
+                                                              float *__restrict__ grad) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const float *e = emb + i * emb_stride, *d = d_emb + i * d_stride;
+    for (int ax = 0; ax < 3; ++ax) {
+        double g = (double)d[ax];
+        for (int f = 0; f < 10; ++f) {
+            const int c = 3 + 6 * f + ax;
+            g += (double)(1 << f) * ((double)d[c] * (double)e[c + 3] - (double)d[c + 3] * (double)e[c]);
+        }
+        grad[i * 3 + ax] = (float)g;
+    }
 }
 
 int nerf_precision(const char *who, int precision) {
@@ -378,14 +433,14 @@ static int nerf_decode_launch(const char *who, const float *packed, const float 
     NB_REQUIRE(n_pts / TILE < (1ll << 31) - 1, "%s: n_rays * n_samples = %lld (< 2^37)", who, n_pts);
     // the attribute belongs to (function, device): set on every call, whichever device and thread this is (a host-side table write)
     const bool fast = precision == NB_PREC_F16X3;
-    const void *fn = fast       ? reinterpret_cast<const void *>(nerf_decode16_kernel)
+    const void *fn = fast       ? reinterpret_cast<const void *>(nerf_decode16_kernel<false>)
                      : want_tap ? reinterpret_cast<const void *>(nerf_decode_kernel<true>)
                                 : reinterpret_cast<const void *>(nerf_decode_kernel<false>);
     const int lds = fast ? LDS_BYTES16 : LDS_BYTES;
     NB_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
     DecodeArgs a = {packed, ray_o, ray_d, z_vals, n_pts, n_samples, raw, tap};
     const dim3 grid(nb_ceil_div(n_pts, TILE));
-    if (fast) hipLaunchKernelGGL(nerf_decode16_kernel, grid, dim3(256), lds, (hipStream_t)stream, a);
+    if (fast) hipLaunchKernelGGL(nerf_decode16_kernel<false>, grid, dim3(256), lds, (hipStream_t)stream, a);
     else if (want_tap) hipLaunchKernelGGL(nerf_decode_kernel<true>, grid, dim3(256), lds, (hipStream_t)stream, a);
     else hipLaunchKernelGGL(nerf_decode_kernel<false>, grid, dim3(256), lds, (hipStream_t)stream, a);
     NB_CHECK_LAUNCH(who);
@@ -401,4 +456,38 @@ extern "C" int nb_nerf_decode(const float *packed, const float *ray_o, const flo
 extern "C" int nb_nerf_decode_tap(const float *packed, const float *ray_o, const float *ray_d, const float *z_vals, int64_t n_rays,
                                   int32_t n_samples, float *raw, float *tap, void *stream) {
     return nerf_decode_launch("nb_nerf_decode_tap", packed, ray_o, ray_d, z_vals, n_rays, n_samples, raw, tap, true, NB_PREC_F32, stream);
+}
+
+extern "C" int nb_nerf_density(const float *packed, const float *pts, int64_t n, float *alpha, int precision, void *stream) {
+    if (int rc = nerf_precision("nb_nerf_density", precision)) return rc;
+    NB_REQUIRE(n >= 0 && n / TILE < (1ll << 31) - 1, "nb_nerf_density: n = %lld (0..2^37 - 1)", (long long)n);
+    if (n == 0) return NB_OK;
+    NB_REQUIRE(packed && pts && alpha, "nb_nerf_density: NULL pointer");
+    NB_REQUIRE(((uintptr_t)packed & 15) == 0, "nb_nerf_density: packed must be 16-byte aligned");
+    NB_REQUIRE((((uintptr_t)pts | (uintptr_t)alpha) & 3) == 0, "nb_nerf_density: pts and alpha must be 4-byte aligned");
+    const bool fast = precision == NB_PREC_F16X3;
+    const void *fn = fast ? reinterpret_cast<const void *>(nerf_decode16_kernel<true>)
+                          : reinterpret_cast<const void *>(nerf_decode_kernel<false, true>);
+    const int lds = fast ? LDS_BYTES16 : LDS_BYTES;
+    NB_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    DecodeArgs a = {packed, pts, nullptr, nullptr, (long long)n, 1, alpha, nullptr};
+    const dim3 grid(nb_ceil_div(n, TILE));
+    if (fast) hipLaunchKernelGGL(nerf_decode16_kernel<true>, grid, dim3(256), lds, (hipStream_t)stream, a);
+    else hipLaunchKernelGGL((nerf_decode_kernel<false, true>), grid, dim3(256), lds, (hipStream_t)stream, a);
+    NB_CHECK_LAUNCH("nb_nerf_density");
+    return NB_OK;
+}
+
+extern "C" int nb_nerf_embed_grad(const float *emb, int64_t emb_stride, const float *d_emb, int64_t d_stride, int64_t n, float *grad,
+                                  void *stream) {
+    NB_REQUIRE(n >= 0 && n / 256 < (1ll << 31) - 1, "nb_nerf_embed_grad: n = %lld (0..2^39 - 1)", (long long)n);
+    NB_REQUIRE(emb_stride >= N_PTS_EMB && d_stride >= N_PTS_EMB, "nb_nerf_embed_grad: emb_stride = %lld, d_stride = %lld (>= %d floats)",
+               (long long)emb_stride, (long long)d_stride, N_PTS_EMB);
+    if (n == 0) return NB_OK;
+    NB_REQUIRE(emb && d_emb && grad, "nb_nerf_embed_grad: NULL pointer");
+    NB_REQUIRE((((uintptr_t)emb | (uintptr_t)d_emb | (uintptr_t)grad) & 3) == 0, "nb_nerf_embed_grad: emb, d_emb and grad must be 4-byte aligned");
+    hipLaunchKernelGGL(nerf_embed_grad_kernel, dim3(nb_ceil_div(n, 256)), dim3(256), 0, (hipStream_t)stream, emb, (long long)emb_stride,
+                       d_emb, (long long)d_stride, (long long)n, grad);
+    NB_CHECK_LAUNCH("nb_nerf_embed_grad");
+    return NB_OK;
 }

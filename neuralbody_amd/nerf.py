@@ -11,7 +11,7 @@ nb_nerf_bwd_chain, the same chain fused into one exact-fp32 kernel, measured slo
 import torch
 import torch.nn as nn
 
-from . import ops
+from . import mesh_extract, ops
 from ._memo import Memo, tkey
 
 # the one configuration the reference ships (configs/nerf/nerf_313.yaml:59-72) and the kernel is built for
@@ -69,6 +69,30 @@ def input_gradients(tap, d_raw, weights):
         ops.sgemm(dz, weights["pts"][L], out=nxt, relu_mask=_cut(tap, T["h"](L - 1)), colsum=col(D["z"](L - 1)))
         dz = nxt
     return dtap, sums
+
+
+def density_input_gradients(tap, weights, dtap=None):
+    """input_gradients' sibling for d_raw = (0, 0, 0, 1), the gradient of the density alone: the view branch passes nothing on, so
+    its three launches (rgb_linear, views_linears[0], feature_linear) are not made and dz7 is alpha_linear's weight under h7's relu
+    mask.  tap [n, 2528], weights (`NerfNetwork.grad_weights`) -> (d-tap [n, 2432] whose dz0 .. dz7 slices are written, dE [n, 64]:
+    the gradient by the 63 point-embedding columns and a zero, held in the first 64 columns of the d-tap's otherwise unused
+    feature slice).  Ten launches, no bias sums; the kernels and their arithmetic are input_gradients' (exact fp32 below 1024 points,
+    bf16 head + remainder pairs from there on), which this function does not touch."""
+    T, D = ops.NERF_TAP, ops.NERF_DTAP
+    n = tap.shape[0]
+    if dtap is None:
+        dtap = torch.empty((n, ops.NERF_DTAP_COLS), dtype=torch.float32, device=tap.device)
+    dz = _cut(dtap, D["z"](7))
+    d_alpha = torch.ones((n, 1), dtype=torch.float32, device=tap.device)
+    ops.sgemm(d_alpha, weights["alpha"], out=dz, relu_mask=_cut(tap, T["h"](7)))
+    for L in range(7, 0, -1):
+        nxt = _cut(dtap, D["z"](L - 1))
+        ops.sgemm(dz, weights["pts"][L], out=nxt, relu_mask=_cut(tap, T["h"](L - 1)))
+        dz = nxt
+    d_emb = dtap[:, D["feature"][0]:D["feature"][0] + 64]
+    ops.sgemm(_cut(dtap, D["z"](0)), weights["emb0"], out=d_emb)
+    ops.sgemm(_cut(dtap, D["z"](5)), weights["emb5"], out=d_emb, beta=1.0)
+    return dtap, d_emb
 
 
 def param_grads(tap, dtap, d_raw, sums=None):
@@ -209,6 +233,70 @@ class NerfNetwork(nn.Module):
         pts[5] = pts[5][:, 63:].contiguous()  # the skip's 63 input columns have no gradient to pass on
         return {"pts": pts, "views_feature": mod.views_linears[0].weight.detach()[:, :256].contiguous(), "feature": w(mod.feature_linear),
                 "alpha": w(mod.alpha_linear), "rgb": w(mod.rgb_linear), "params": [p.detach() for p in mod.parameters()]}
+
+    def grad_weights(self, model=""):
+        """What density_input_gradients multiplies by, cached per module and parameter version: pts_linears[1..7] (of the skip layer
+        its 256 h columns), alpha_linear, and the two matrices that carry a gradient to the embedding, pts_linears[0] [256,63] and
+        the skip's first 63 columns, each as a contiguous zero-padded [256,64] matrix (rows of 63 floats are not 16-byte aligned)."""
+        mod = self._module(model)
+
+        def build():
+            w = [lin.weight.detach() for lin in mod.pts_linears]
+            pad = lambda m: torch.nn.functional.pad(m, (0, 1)).contiguous()  # noqa: E731
+            pts = [None] + [w[i] if i != 5 else w[5][:, 63:].contiguous() for i in range(1, 8)]
+            return {"pts": pts, "alpha": mod.alpha_linear.weight.detach(), "emb0": pad(w[0]), "emb5": pad(w[5][:, :63])}
+
+        return self._memo.get("grad_fine" if model == "fine" else "grad", (tkey(*mod.parameters()),), build)
+
+    def density(self, pts, model=""):
+        """lib/networks/nerf_mesh.py:45-54,125-138: alpha [n] at the points pts [n,3], the raw output of alpha_linear (no relu), by
+        nb_nerf_density: the trunk alone, the bits of forward(...)[..., 3] at the same points.  Inference only, like `decode`."""
+        self._inference_only("NerfNetwork.density")
+        if pts.dim() != 2 or pts.shape[-1] != 3:
+            raise ValueError("pts must be [n,3], got %s" % (tuple(pts.shape),))
+        return ops.nerf_density(self.packed(model), pts.float().contiguous(), self.nerf_precision())
+
+    # density_gradient: tap plus d-tap of one chunk stay below this many bytes (a bound on memory, not a tuning knob)
+    GRADIENT_CHUNK_BYTES = 1 << 30
+
+    def density_gradient(self, pts, model=""):
+        """(alpha [n], d alpha / d p [n,3]) at the points pts [n,3], without autograd and on an inference-only network: the forward
+        is nb_nerf_decode_tap (always f32, the points as rays of depth 0 like `forward`), the chain density_input_gradients, the last
+        step nb_nerf_embed_grad on the tap's own embedding columns.  alpha has the bits of density() in 'f32'.  In chunks of
+        GRADIENT_CHUNK_BYTES // (tap + d-tap bytes per point) = 54 120 points."""
+        self._inference_only("NerfNetwork.density_gradient")
+        if pts.dim() != 2 or pts.shape[-1] != 3:
+            raise ValueError("pts must be [n,3], got %s" % (tuple(pts.shape),))
+        pts = pts.float().contiguous()
+        n, dev = pts.shape[0], pts.device
+        alpha = torch.empty((n,), dtype=torch.float32, device=dev)
+        grad = torch.empty((n, 3), dtype=torch.float32, device=dev)
+        if n == 0:
+            return alpha, grad
+        mod = self._module(model)
+        params = {k: v.detach() for k, v in mod.named_parameters()}
+        packed = self.packed(model) if self.nerf_precision() == "f32" else \
+            self._memo.get("grad_packed_fine" if model == "fine" else "grad_packed", (tkey(*mod.parameters()),),
+                           lambda: ops.nerf_pack(params, "f32"))
+        weights = self.grad_weights(model)
+        chunk = max(1, self.GRADIENT_CHUNK_BYTES // (4 * (ops.NERF_TAP_COLS + ops.NERF_DTAP_COLS)))
+        m = min(n, chunk)
+        tap = torch.empty((m, ops.NERF_TAP_COLS), dtype=torch.float32, device=dev)
+        dtap = torch.empty((m, ops.NERF_DTAP_COLS), dtype=torch.float32, device=dev)
+        raw = torch.empty((m, 1, 4), dtype=torch.float32, device=dev)
+        zero = torch.zeros((m, 1), dtype=torch.float32, device=dev)
+        first = ops.NERF_TAP["pts"][0]
+        for i in range(0, n, chunk):
+            k = min(chunk, n - i)
+            o = pts[i:i + k]
+            # the direction is not read by the trunk; any non-zero one keeps d / |d| finite
+            d = torch.zeros_like(o)
+            d[:, 2] = 1.0
+            ops.nerf_decode_tap(packed, o, d, zero[:k], out=raw[:k], tap=tap[:k])
+            alpha[i:i + k] = raw[:k, 0, 3]
+            _, d_emb = density_input_gradients(tap[:k], weights, dtap[:k])
+            ops.nerf_embed_grad(tap[:k, first:first + 64], d_emb, out=grad[i:i + k])
+        return alpha, grad
 
     def _wants_grad(self, model):
         return self.trainable and torch.is_grad_enabled() and any(p.requires_grad for p in self._module(model).parameters())
@@ -391,3 +479,59 @@ def _width(key, cfg):
     """Last dimension of an output of VolumeRenderer.render (needed only for an empty batch, where no row shows it)."""
     T = int(cfg.N_samples) + int(cfg.N_importance)
     return {"rgb_map": 3, "rgb0": 3, "raw": 4 * T, "z_vals": T, "weights": T}.get(key, 1)
+
+
+class NerfMeshConfig:
+    """What NerfMeshRenderer reads of a config: mesh_th and N_importance of configs/nerf/nerf_313.yaml, and the keys RendererMesh
+    has for its options (not reference keys, off unless set)."""
+
+    def __init__(self, mesh_th=5.0, N_importance=128, mesh_backend="auto", mesh_components="all", mesh_color=False,
+                 mesh_normals="faces"):
+        self.mesh_th, self.N_importance, self.mesh_backend = float(mesh_th), int(N_importance), str(mesh_backend)
+        self.mesh_components, self.mesh_color, self.mesh_normals = mesh_components, bool(mesh_color), str(mesh_normals)
+
+
+class NerfMeshRenderer:
+    """lib/networks/renderer/volume_mesh_renderer.py:84-107 over a NerfNetwork: the density of the baseline on the lattice of the
+    mesh dataset and the mesh of its iso-surface cube == cfg.mesh_th.  The cube holds the raw output of alpha_linear (the reference
+    does not relu it) at the lattice points flagged `inside` and 0 elsewhere, padded by 10.  The module asked is the fine one when
+    cfg.N_importance > 0 and the coarse one otherwise (volume_mesh_renderer.py:50-55).  The density is ONE nb_nerf_density launch,
+    the trunk of the MLP alone (the reference chunks cfg.chunk points per call); the lattice forms and everything behind the cube
+    are RendererMesh's (mesh_extract), so cfg.mesh_components, cfg.mesh_color, cfg.mesh_normals: field and the visualizer's
+    mesh_render work as they do there.  Colours: one NerfNetwork.forward at the vertices looking along -normal; field normals:
+    NerfNetwork.density_gradient."""
+
+    PAD = mesh_extract.PAD
+
+    def __init__(self, net, cfg=None):
+        self.net = net
+        self.cfg = cfg if cfg is not None else NerfMeshConfig()
+
+    def model(self):
+        """'fine' with cfg.N_importance > 0, '' otherwise."""
+        return "fine" if int(self.cfg.N_importance) > 0 else ""
+
+    def _field(self):
+        model = self.model()
+
+        def raw(wpts, viewdir):  # [1,V,3] each: every vertex its own direction, so V "rays" of one sample
+            return self.net.forward(wpts[0][:, None].contiguous(), viewdir[0].contiguous(), model=model)
+
+        return mesh_extract.FieldQueries(density=lambda wpts: self.net.density(wpts, model=model), raw=raw,
+                                         gradient=lambda wpts: self.net.density_gradient(wpts, model=model)[1])
+
+    def density_cube(self, batch, pad=PAD):
+        """-> DEVICE float32 [X+2*pad, Y+2*pad, Z+2*pad] (mesh_extract.lattice_cube: the reference dataset's `pts` + `inside`, or
+        `axis_x / axis_y / axis_z` + the device-carved `inside` of plugins/light_stage_mesh_dataset.py)."""
+        return mesh_extract.lattice_cube(batch, pad, self._field().density)
+
+    def extract_mesh(self, batch, world=False, cube=None, components="all", colors=False, normals="faces"):
+        """RendererMesh.extract_mesh's semantics (mesh_extract.mesh_from_cube): DEVICE (vertices, triangles), or a ColoredMesh."""
+        if cube is None:
+            cube = self.density_cube(batch)
+        return mesh_extract.mesh_from_cube(batch, cube, self.cfg.mesh_th, self._field(), world=world, components=components,
+                                           colors=colors, normals=normals, pad=self.PAD)
+
+    def render(self, batch):
+        """volume_mesh_renderer.py:84-107 -> {"cube", "mesh"}, as RendererMesh.render (mesh_extract.render_mesh)."""
+        return mesh_extract.render_mesh(self.cfg, batch, lambda: (self.density_cube(batch), self._field()))

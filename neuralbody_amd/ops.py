@@ -1972,6 +1972,38 @@ def nerf_decode(packed, ray_o, ray_d, z_vals, precision="f32", out=None):
     return out
 
 
+def nerf_density(packed, pts, precision="f32", out=None):
+    """nb_nerf_density: alpha [n] of the packed Nerf module's trunk at the points pts [n,3] (alpha_linear's raw output, no relu):
+    the bits of nerf_decode(...)[..., 3] at the same points."""
+    prec = _nerf_precision(precision)
+    _req(pts, torch.float32, (None, 3), "pts")
+    n = pts.shape[0]
+    _req(packed, torch.float32, (nerf_pack_size(precision),), "packed")
+    if out is None:
+        out = torch.empty((n,), dtype=torch.float32, device=pts.device)
+    _req(out, torch.float32, (n,), "out")
+    with torch.cuda.device(pts.device):
+        check(_lib.lib().nb_nerf_density(ptr(packed), ptr(pts), n, ptr(out), prec, _stream()), "nb_nerf_density")
+    return out
+
+
+def nerf_embed_grad(emb, d_emb, out=None):
+    """nb_nerf_embed_grad: emb [n,>=63] the forward's point-embedding columns and d_emb [n,>=63] the gradient by them (both may be
+    column slices of wider matrices) -> grad [n,3], the gradient by the point."""
+    _mat(emb, "emb")
+    _mat(d_emb, "d_emb")
+    n = emb.shape[0]
+    if emb.shape[1] < 63 or d_emb.shape[1] < 63 or d_emb.shape[0] != n or d_emb.device != emb.device:
+        raise ValueError("emb and d_emb must be [n, >= 63] on one device, got %s and %s" % (tuple(emb.shape), tuple(d_emb.shape)))
+    if out is None:
+        out = torch.empty((n, 3), dtype=torch.float32, device=emb.device)
+    _req(out, torch.float32, (n, 3), "out")
+    with torch.cuda.device(emb.device):
+        check(_lib.lib().nb_nerf_embed_grad(ptr(emb), max(emb.stride(0), 63), ptr(d_emb), max(d_emb.stride(0), 63), n, ptr(out),
+                                            _stream()), "nb_nerf_embed_grad")
+    return out
+
+
 NERF_TAP_COLS, NERF_DTAP_COLS = 2528, 2432  # NB_NERF_TAP_COLS, NB_NERF_DTAP_COLS
 # column slices of the tap (include/nb_hip.h: nb_nerf_decode_tap) and of the d-tap (nb_nerf_bwd_chain), as (first, width)
 NERF_TAP = {"h": lambda i: (256 * i, 256), "feature": (2048, 256), "V": (2304, 128), "pts": (2432, 63), "view": (2496, 27)}

@@ -9,12 +9,11 @@ The overridable pieces the reference's subclasses rely on are kept with the same
 get_density_color, get_pixel_value.  get_pixel_value (points decoded through the Network API, then
 nb_composite) is what a subclass that culls samples would call; render() itself uses the fused path.
 """
-import collections
-
 import torch
 
-from . import ops
+from . import mesh_extract, ops
 from ._memo import Memo, tkey
+from .mesh_extract import ColoredMesh  # noqa: F401  (RendererMesh.extract_mesh(colors=True) returns one)
 
 
 class RenderConfig:
@@ -47,10 +46,6 @@ class RenderConfig:
         # hierarchical sampling (lib/config/config.py N_importance, volume_renderer.py:82-104; no light-stage config of the reference sets
         # it): render() puts this many more samples per ray where the first pass found the surface (`_importance_pass`); 0 = off
         self.N_importance = int(N_importance)
-
-
-class ColoredMesh(collections.namedtuple("ColoredMesh", "vertices triangles rgb_f rgb_u8 wpts viewdir normals")):
-    """RendererMesh.extract_mesh(colors=True): device tensors; the first two are what it returns without colours."""
 
 
 class SpInput(dict):
@@ -571,7 +566,7 @@ class RendererMesh(Renderer):
     def density_cube(self, batch, pad=PAD):
         """-> DEVICE float32 tensor [X+2*pad, Y+2*pad, Z+2*pad]: alpha at the inside lattice points, 0 elsewhere.
         A batch that carries the lattice's axes (`axis_x`, `axis_y`, `axis_z`: neuralbody_amd/mesh_lattice.py) never holds the
-        [X,Y,Z,3] points: see `_density_cube_axes`.  A batch with `pts` is the reference dataset's."""
+        [X,Y,Z,3] points (mesh_extract.lattice_cube).  A batch with `pts` is the reference dataset's."""
         return self._density_cube(batch, pad)[0]
 
     def _density_cube(self, batch, pad=PAD):
@@ -585,59 +580,23 @@ class RendererMesh(Renderer):
                 made.append((self.net.encode_sparse_voxels(sp_input), sp_input))
             return made[0]
 
-        if "axis_x" in batch:
-            return self._density_cube_axes(batch, pad, volumes), volumes
-        pts = batch["pts"]
-        inside = batch["inside"][0].bool()
-        wpts = pts[0][inside][None].contiguous()
-        feature_volume, sp_input = volumes()
-        alpha = self.net.calculate_density(wpts, feature_volume, sp_input)
-        cube = torch.zeros(pts.shape[1:-1], dtype=torch.float32, device=pts.device)
-        cube[inside] = alpha[0, :, 0]
-        return torch.nn.functional.pad(cube, (pad,) * 6), volumes
+        return mesh_extract.lattice_cube(batch, pad, self._field(volumes).density), volumes
 
-    @staticmethod
-    def _axes(batch):
-        """The lattice's three axis vectors of a collated batch (batch size 1, like `pts[0]` above)."""
-        axes = [batch[k] for k in ("axis_x", "axis_y", "axis_z")]
-        if any(a.dim() != 2 or a.shape[0] != 1 for a in axes):
-            raise ValueError("axis_x / axis_y / axis_z must be [1, n] (test.batch_size 1), got %s" % (
-                [tuple(a.shape) for a in axes],))
-        return [a[0].contiguous() for a in axes]
+    def _field(self, volumes):
+        """The three field queries of mesh_extract over this network and the frame's feature volumes (`volumes()`, made when first
+        asked): ONE nb_decode_points launch each, Network.calculate_density / _density_color / _density_gradient."""
+        return mesh_extract.FieldQueries(
+            density=lambda wpts: self.net.calculate_density(wpts[None], *volumes()),
+            raw=lambda wpts, viewdir: self.net.calculate_density_color(wpts, viewdir, *volumes()),
+            gradient=lambda wpts: self.net.calculate_density_gradient(wpts[None].contiguous(), *volumes())[1][0])
 
-    def _density_cube_axes(self, batch, pad, volumes):
-        """nb_lattice_gather -> calculate_density -> nb_lattice_scatter into the padded cube.  The count pass of the gather runs
-        first (cap 0) and its 8-byte `n_out` is the one read-back: it sizes the point list, like `pts[0][inside]` does."""
-        axes = self._axes(batch)
-        inside = batch["inside"][0]
-        inside = (inside if inside.dtype == torch.uint8 else (inside != 0).to(torch.uint8)).contiguous()
-        dims = [int(a.shape[0]) for a in axes]
-        scratch = ops.lattice_scratch(dims, inside.device)
-        total = int(ops.lattice_gather(axes, inside, scratch=scratch)[1].item())
-        if total == 0:  # nothing to decode: the zero cube
-            return torch.zeros([d + 2 * pad for d in dims], dtype=torch.float32, device=inside.device)
-        wpts = torch.empty((total, 3), dtype=torch.float32, device=inside.device)
-        lin = torch.empty(total, dtype=torch.int32, device=inside.device)
-        ops.lattice_gather(axes, inside, wpts, lin, scratch=scratch)
-        feature_volume, sp_input = volumes()
-        alpha = self.net.calculate_density(wpts[None], feature_volume, sp_input)
-        return ops.lattice_scatter(alpha, lin, dims, pad)
+    _axes = staticmethod(mesh_extract.lattice_axes)
 
     def _world_frame(self, batch, like):
-        """(step [3], origin [3]) of the lattice as tensors like `like`: the spacing read from the lattice and wbounds[0]."""
-        if "pts" in batch:
-            pts = batch["pts"]
-            step = torch.stack([pts[0, 1, 0, 0, 0] - pts[0, 0, 0, 0, 0], pts[0, 0, 1, 0, 1] - pts[0, 0, 0, 0, 1],
-                                pts[0, 0, 0, 1, 2] - pts[0, 0, 0, 0, 2]]).to(like)
-        else:
-            step = torch.stack([a[1] - a[0] for a in self._axes(batch)]).to(like)
-        return step, batch["wbounds"][0, 0].to(like)
+        return mesh_extract.world_frame(batch, like)
 
     def _to_world(self, vertices, batch, pad=PAD):
-        """Lattice index units of the padded cube -> world units: (v - pad) * step + wbounds[0] (the two lines the reference
-        leaves commented out, if_mesh_renderer.py:49-50, with the step read from the lattice instead of the literal 0.005)."""
-        step, origin = self._world_frame(batch, vertices)
-        return (vertices - float(pad)) * step + origin
+        return mesh_extract.to_world(vertices, batch, pad)
 
     def extract_mesh(self, batch, world=False, cube=None, components="all", colors=False, volumes=None, normals="faces"):
         """-> DEVICE (vertices [V,3] float32, triangles [T,3] int32) of the iso-surface cube == cfg.mesh_th (ops.marching_cubes;
@@ -654,40 +613,15 @@ class RendererMesh(Renderer):
         normals (with colors): "faces" — the area-weighted face normals of the mesh (ops.mesh_vertex_normals); "field" — the normal
         of the density field itself, -grad sigma / |grad sigma| at the world vertices (Network.calculate_density_gradient on the same
         feature volumes, normalised by nb_normal_composite with every vertex a ray of one sample); a vertex whose gradient is zero or
-        not finite keeps its face normal."""
+        not finite keeps its face normal.  The steps behind the cube are mesh_extract.mesh_from_cube, shared with NerfMeshRenderer."""
         if normals not in ("faces", "field"):
             raise ValueError("normals must be 'faces' or 'field', got %r" % (normals,))
         if cube is None:
             cube, volumes = self._density_cube(batch)
-        vertices, triangles = ops.marching_cubes(cube.contiguous(), self.cfg.mesh_th)
-        if ops.mesh_components_fraction(components) is not None:
-            scratch = ops.mesh_clean_scratch(vertices.shape[0], triangles.shape[0], vertices.device)
-            label = ops.mesh_components(triangles, vertices.shape[0], scratch=scratch)
-            keep, _ = ops.mesh_component_select(label, triangles, components, scratch=scratch)
-            vertices, triangles = ops.mesh_compact(vertices, triangles, keep, scratch=scratch)
-        if not colors:
-            return (self._to_world(vertices, batch) if world else vertices), triangles
-        if volumes is None:  # a cube from elsewhere: its frame is encoded here
-            volumes = self._volumes(batch)
-        wverts = self._to_world(vertices, batch)
-        face_normals = ops.mesh_vertex_normals(wverts, triangles)
-        if normals == "field" and wverts.shape[0]:
-            feature_volume, sp_input = volumes()
-            grad = self.net.calculate_density_gradient(wverts[None].contiguous(), feature_volume, sp_input)[1][0]
-            V = wverts.shape[0]
-            unit, _ = ops.normal_composite(torch.arange(V, dtype=torch.int32, device=wverts.device), grad,
-                                           torch.ones((V, 1), dtype=torch.float32, device=wverts.device))
-            normals = torch.where((unit != 0).any(1, keepdim=True), unit, face_normals).contiguous()
-        else:
-            normals = face_normals
-        step, origin = self._world_frame(batch, vertices)
-
-        def decode(wpts, viewdir):
-            feature_volume, sp_input = volumes()
-            return self.net.calculate_density_color(wpts, viewdir, feature_volume, sp_input)
-
-        rgb_f, rgb_u8, wpts, viewdir = ops.mesh_vertex_colors(vertices, normals, step.contiguous(), origin.contiguous(), self.PAD, decode)
-        return ColoredMesh(wverts if world else vertices, triangles, rgb_f, rgb_u8, wpts, viewdir, normals)
+        # (a cube from elsewhere without its volumes: its frame is encoded when the colours are asked for)
+        field = lambda: self._field(volumes if volumes is not None else self._volumes(batch))  # noqa: E731
+        return mesh_extract.mesh_from_cube(batch, cube, self.cfg.mesh_th, field, world=world, components=components, colors=colors,
+                                           normals=normals, pad=self.PAD)
 
     def _volumes(self, batch):
         sp_input = self.prepare_sp_input(batch)
@@ -695,48 +629,10 @@ class RendererMesh(Renderer):
         return lambda: held
 
     def render(self, batch):
-        """if_mesh_renderer.py:26-54 -> {"cube", "mesh"}.  cfg.mesh_components / cfg.mesh_color / cfg.mesh_normals: field (YAML-only
-        keys like mesh_render, absent = off) ask for `extract_mesh`'s clean-up, vertex colours and field normals (TriMesh.vertex_normals,
-        written as nx ny nz and handed to the turntable): with any of them set the mesh is extracted on the device
-        whatever cfg.mesh_backend says (PyMCubes has neither), and `mesh` is a mesh.TriMesh, the class that carries
-        vertex_colors."""
-        backend = getattr(self.cfg, "mesh_backend", "auto")
-        if backend not in ("auto", "device"):
-            raise ValueError("mesh_backend must be 'auto' or 'device', got %r" % (backend,))
-        components, colors = getattr(self.cfg, "mesh_components", "all"), bool(getattr(self.cfg, "mesh_color", False))
-        normals = str(getattr(self.cfg, "mesh_normals", "faces"))
-        if ops.mesh_components_fraction(components) is not None or colors or normals == "field":
-            from .mesh import TriMesh
+        """if_mesh_renderer.py:26-54 -> {"cube", "mesh"} (mesh_extract.render_mesh has the keys it reads: mesh_backend,
+        mesh_components, mesh_color, mesh_normals)."""
+        def cube_and_field():
+            cube, volumes = self._density_cube(batch)
+            return cube, self._field(volumes)
 
-            cube_dev, volumes = self._density_cube(batch)
-            # (the field normals come with the colour query: the colour head is asked along them; the colours are kept only if asked for)
-            mesh = self.extract_mesh(batch, cube=cube_dev, components=components, colors=colors or normals == "field", volumes=volumes,
-                                     normals=normals)
-            cube = cube_dev.double().cpu().numpy()
-            return {"cube": cube, "mesh": TriMesh(mesh[0].double().cpu().numpy(), mesh[1].cpu().numpy(),
-                                                  vertex_colors=mesh.rgb_u8.cpu().numpy() if colors else None,
-                                                  vertex_normals=mesh.normals.cpu().numpy() if normals == "field" else None)}
-        mcubes = None
-        if backend == "auto":
-            try:
-                import mcubes  # CPU marching cubes, as in the reference (if_mesh_renderer.py:6,46)
-            except ImportError:
-                mcubes = None
-        if mcubes is not None:
-            import trimesh
-
-            cube = self.density_cube(batch).double().cpu().numpy()
-            vertices, triangles = mcubes.marching_cubes(cube, self.cfg.mesh_th)
-            return {"cube": cube, "mesh": trimesh.Trimesh(vertices, triangles)}
-
-        cube_dev = self.density_cube(batch)
-        vertices, triangles = self.extract_mesh(batch, cube=cube_dev)
-        cube = cube_dev.double().cpu().numpy()  # the float64 ndarray the reference's evaluator slices
-        vertices, triangles = vertices.double().cpu().numpy(), triangles.cpu().numpy()
-        try:
-            import trimesh
-        except ImportError:
-            from .mesh import TriMesh
-
-            return {"cube": cube, "mesh": TriMesh(vertices, triangles)}
-        return {"cube": cube, "mesh": trimesh.Trimesh(vertices, triangles)}
+        return mesh_extract.render_mesh(self.cfg, batch, cube_and_field)
